@@ -7,22 +7,26 @@ One "step" = one complete solve of that batch (init kernel + chunked stepping ke
 trajectory has reached t_end).  Metric: accepted RK steps per second, aggregate over the batch and
 over all ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last step's results when --dump-outputs is given
+(DIR/<name>.npy, float64, at most 64 MB in all: a fixed, seeded sample of trajectories when the batch is larger) and
+prints the result line.  Every secondary measurement runs with --full only.
 
 N > 1 (BASELINE config C4 as written): one process per GPU; the SAME batch of 100 000 trajectories is cut into N
 contiguous shards after a fixed permutation (trajectories are independent, so there is no data-path collective) and the
-end-state arenas are gathered with ONE RCCL all-gather per step inside the timed region: "scaling": "strong".  A weak-
-scaling figure (100 000 trajectories PER GPU) is measured in the same run and reported as the "weak" object.
+end-state arenas are gathered with ONE RCCL all-gather per step inside the timed region: "scaling": "strong".  With
+--full a weak-scaling figure (100 000 trajectories PER GPU) is measured in the same run and reported as the "weak" object.
 
-Timing: the headline steps run with options.profile = 0; the per-launch HIP-event durations that feed the roofline
-objects come from a separate instrumented pass of the same K steps; "wall_ms_with_d2h" repeats the steps with a D2H
-copy of the results into pinned host memory after every solve.
+Timing: the headline steps run with options.profile = 0.  With --full, the per-launch HIP-event durations that feed the
+roofline objects come from a separate instrumented pass of the same K steps, and "wall_ms_with_d2h" repeats the steps
+with a D2H copy of the results into pinned host memory after every solve.
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (HBM view, as the contract asks),
+Rank 0 prints ONE JSON line.  Extra objects with --full: "roofline" (HBM view, as the contract asks),
 "roofline_fp64" (counted FP64 flops), "roofline_issue" (the resource that actually binds the stepping kernel:
-vector-instruction issue, from the committed SQ-counter profile) and "cpu_baseline"
-(the CPU oracle, i.e. the C restatement of the reference algorithm, timed on this host's cores).
+vector-instruction issue, from the committed SQ-counter profile), the FMA-mode, pipelined and output-mode figures and
+"cpu_baseline" (the CPU oracle, i.e. the C restatement of the reference algorithm, timed on this host's cores).
 """
 import argparse
 import json
@@ -102,6 +106,12 @@ def main():
     ap.add_argument("--workload", choices=["c2", "c3", "c5"], default="c2",
                     help="c2 = BASELINE headline (default; with --gpus N > 1 it is C4: the same batch sharded); "
                          "c3 = 1M Van der Pol DOP853 rtol 1e-8; c5 = 10k stiff Van der Pol BDF")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: instrumented and D2H passes with the roofline objects, weak "
+                         "scaling (N > 1), FMA-mode and pipelined figures, output modes, CPU baseline and accuracy vs truth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the end-state arrays of the last step as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of trajectories, with its indices in sample_index.npy, beyond 64 MB)")
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the secondary weak-scaling figure")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fast", action="store_true", help="skip the secondary fast-FP-mode / pipelined measurements")
@@ -109,7 +119,7 @@ def main():
                     help="N = 1: measure the device DefaultSolOut output modes of the workload instead of the end-state "
                          "headline (t_eval: 128 samples per trajectory; csr_log: every accepted step, count + fill passes; "
                          "dense: step log + dense-output segments; events: a hiprtc CR3BP with the y = 0 crossing event); "
-                         "the default run carries t_eval and csr_log as the secondary object `outputs`")
+                         "a --full run carries t_eval and csr_log as the secondary object `outputs`")
     args = ap.parse_args()
 
     # RCCL prints a version banner on stdout while the process group comes up; keep stdout clean for the ONE JSON
@@ -136,7 +146,7 @@ def main():
 
     import ivp_amd
     from ivp_amd import workloads as W
-    from ivp_amd.distributed import ResultArena, run_steps, shard_bounds
+    from ivp_amd.distributed import ResultArena, _unpermute, run_steps, shard_bounds
 
     if args.fp == "fast":
         args.fp = "fma"
@@ -210,89 +220,38 @@ def main():
     nstep_rank = float(out.nstep.sum().item())
     nrej_rank = float(out.nrejct.sum().item())
     elapsed, total_acc = reduce_max_sum(el, acc_rank)
-    gathered_ok = None
+    gathered_ok = g = None
     if og is not None:   # every rank now holds every shard's end state: check the gathered status words and counters
         g = ResultArena(n_state, hi - lo, dev).split(og.gathered[(og.steps - 1) & 1], [hi - lo] * world)
         gathered_ok = bool((g["status"] == 0).all().item()) and int(g["naccpt"].sum().item()) == int(total_acc)
+    if args.dump_outputs and rank == 0:
+        if g is not None:   # the gathered batch, back in the original trajectory order
+            arrays = _unpermute({k: v.cpu().numpy() for k, v in g.items()}, W.shard_permutation(B), B)
+        else:
+            arrays = {k: getattr(out, k) for k in DUMP_FIELDS if getattr(out, k, None) is not None}
+        dump_outputs(args.dump_outputs, arrays)
 
-    # ---- instrumented pass (NOT the headline): per-launch HIP-event durations for the roofline objects ----
-    el_p, out_p, acc, _ = run_case(*sh, profile=1, with_gather=False)
-    # ---- results on the host: the same steps followed by a D2H copy of the end-state arena into pinned memory ----
-    el_h, _, _, _ = run_case(*sh, profile=0, with_gather=False, with_d2h=True)
-    el_h, _ = reduce_max_sum(el_h, 0)
-
-    # ---- WEAK scaling (secondary figure, N > 1): B trajectories PER RANK (a parameter sweep: rank r takes seed + r) ----
     weak = None
-    if world > 1 and not args.no_weak:
-        yw, pw, _, t1w = getattr(W, wl["gen"])(B, seed=wl["seed"] + rank)
-        el_w, out_w, _, _ = run_case(yw, pw, t1w, profile=0, with_gather=True)
-        el_w, acc_w = reduce_max_sum(el_w, int(out_w.naccpt.sum().item()))
-        weak = {"scaling": "weak", "trajectories_per_gpu": B, "value": acc_w * args.steps / el_w, "unit": "steps/s",
-                "ms_per_step": el_w / args.steps * 1e3,
-                "note": "every rank integrates its own batch of the full size (seed + rank) and all-gathers its end-state arena"}
+    if args.full:
+        # ---- instrumented pass (NOT the headline): per-launch HIP-event durations for the roofline objects ----
+        el_p, out_p, acc, _ = run_case(*sh, profile=1, with_gather=False)
+        # ---- results on the host: the same steps followed by a D2H copy of the end-state arena into pinned memory ----
+        el_h, _, _, _ = run_case(*sh, profile=0, with_gather=False, with_d2h=True)
+        el_h, _ = reduce_max_sum(el_h, 0)
+
+        # ---- WEAK scaling (secondary figure, N > 1): B trajectories PER RANK (a parameter sweep: rank r takes seed + r) ----
+        if world > 1 and not args.no_weak:
+            yw, pw, _, t1w = getattr(W, wl["gen"])(B, seed=wl["seed"] + rank)
+            el_w, out_w, _, _ = run_case(yw, pw, t1w, profile=0, with_gather=True)
+            el_w, acc_w = reduce_max_sum(el_w, int(out_w.naccpt.sum().item()))
+            weak = {"scaling": "weak", "trajectories_per_gpu": B, "value": acc_w * args.steps / el_w, "unit": "steps/s",
+                    "ms_per_step": el_w / args.steps * 1e3,
+                    "note": "every rank integrates its own batch of the full size (seed + rank) and all-gathers its end-state arena"}
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_acc * args.steps / elapsed
-        launches, kern_ms, coop_ms, coop_launches = acc["launches"], acc["kern_ms"], acc["coop_ms"], acc["coop_launches"]
         attempts = nstep_rank * args.steps   # DOPRI5/DOP853/BDF: nstep counts every attempt (dopri5.rs:285)
-        avg_launch_ms = kern_ms / max(launches, 1)
-        attempts_per_launch = attempts / max(launches, 1)
-        lanes_per_launch = acc["lane_launches"] / max(launches, 1)  # trajectories that load + store their state
-        flop_per_attempt = wl["flop_per_attempt"]
-        bytes_per_launch = lanes_per_launch * bytes_per_lane_launch(n_state, prob.n_params, args.workload)
-        gbs = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
-        tflops = (attempts_per_launch * flop_per_attempt / (avg_launch_ms * 1e-3) / 1e12) if (avg_launch_ms > 0 and flop_per_attempt) else None
-        # PMC-derived figures come from committed profiles of this command (separate rocprofv3 --pmc passes: counters cannot be
-        # collected inside a timed run).  Each profile is stamped with the hash of the kernel sources it was taken on; a
-        # profile of OTHER kernels than the ones just timed is reported as stale and nothing is derived from it.
-        sha_now = kernel_sources_sha256()
-        traffic = traffic_src = None
-        traffic_stale = None
-        pmc_name = f"{PROFILE_ROUND}_pmc_hbm_bytes_per_launch_{args.fp}.json"
-        pmc = os.path.join(ROOT, "profiles", pmc_name)
-        if os.path.exists(pmc) and args.workload == "c2" and world == 1 and B == 100_000:
-            try:
-                j = json.load(open(pmc))
-                traffic_stale = j.get("kernel_sources_sha256") != sha_now
-                if not traffic_stale:
-                    traffic = j.get("hbm_bytes_per_launch")
-                traffic_src = f"profiles/{pmc_name} (" + str(j.get("run", "rocprofv3 --pmc passes of tools/profile_c2.sh")) + \
-                              "): PMC counters of a separate profiled run of this command, not of this process" + \
-                              ("; STALE: taken on other kernel sources than this run's (hash mismatch), not used" if traffic_stale else "")
-            except Exception:
-                traffic = None
-        # VALU issue view of the dominant kernel: the thread-per-trajectory stepping kernel is bound by vector-instruction
-        # issue (one wave64 FP64 instruction per 4 cycles per SIMD at best), not by bytes or by counted flops (strict mode
-        # spends separate multiply and add instructions, 11 on a division, 18 on a square root).  Instructions per launch
-        # come from the committed SQ-counter profile of this command (profiles/<PROFILE_ROUND>_sq_counters_<workload>_<fp>.json,
-        # SQ_INSTS_VALU, tools/profile_sq.sh), the launch duration is this run's.
-        issue = None
-        sq_name = f"{PROFILE_ROUND}_sq_counters_{args.workload}_{args.fp}.json"
-        sqf = os.path.join(ROOT, "profiles", sq_name)
-        chunk_launches = launches - coop_launches
-        chunk_ms = (kern_ms - coop_ms) / max(chunk_launches, 1)
-        if os.path.exists(sqf) and world == 1 and B == wl["B"] and chunk_ms > 0:
-            try:
-                sq = json.load(open(sqf))
-                if sq.get("kernel_sources_sha256") != sha_now:
-                    raise LookupError("stale")
-                ent = next(v for k, v in sq.items() if "chunk_kernel_t" in k and "coop" not in k)
-                valu = float(ent["mean_per_dispatch"]["SQ_INSTS_VALU"])
-                if "per_solve" in ent:   # instructions of a whole solve / this run's launches per solve: robust against a
-                    valu = float(ent["per_solve"]["SQ_INSTS_VALU"]) / max(chunk_launches / args.steps, 1e-9)   # different cut into launches
-                peak = 256 * 4 * 2.4e9 / 4.0   # SIMDs x (clock / 4 cycles per wave64 instruction), at the 2.4 GHz peak clock
-                issue = {"bound": "valu_issue", "kernel": "chunk_kernel_t", "achieved": valu / (chunk_ms * 1e-3), "peak": peak,
-                         "unit": "wave-instructions/s", "frac": valu / (chunk_ms * 1e-3) / peak, "valu_instructions_per_launch": valu,
-                         "avg_launch_ms": chunk_ms,
-                         "source": f"profiles/{sq_name} (SQ_INSTS_VALU per launch, separate rocprofv3 --pmc "
-                                   "run of this command) / this run's launch duration"}
-            except LookupError:
-                issue = {"bound": "valu_issue", "kernel": "chunk_kernel_t", "stale": True,
-                         "source": f"profiles/{sq_name}: taken on other kernel sources than this run's (hash mismatch), nothing derived"}
-            except Exception:
-                issue = None
-        fp64_frac = (tflops / FP64_PEAK_TFLOPS) if tflops is not None else None
         res = {
             "metric": wl["metric"],
             "value": value,
@@ -316,66 +275,26 @@ def main():
                 "parallelism": f"dp{world} (independent shards" + (", one RCCL all-gather of the end states per step)" if world > 1 else ")"),
             },
             "wall_ms_to_t_end": ms_per_step,
-            "wall_ms_with_d2h": el_h / args.steps * 1e3,
-            "instrumented_ms_per_step": el_p / args.steps * 1e3,
-            "timing_note": "value / ms_per_step: options.profile = 0 (no per-launch events); roofline launch durations come "
-                           "from a separate instrumented pass of the same K steps (instrumented_ms_per_step, this rank)",
             "accepted_steps_per_batch": total_acc,
             "all_success": ok,
             "status_counts": status_counts,
             "gathered_ok": gathered_ok,
-            "wave_lane_utilisation": attempts / acc["slots"] if acc["slots"] else None,
             "attempts_per_s": attempts / el * 1.0, "rejection_ratio": nrej_rank / max(nstep_rank, 1.0),
-            "roofline": {
-                "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                # the resource that actually bounds this path: FP64 vector arithmetic, counted flops of the
-                # whole solve over its wall time -- the HBM figures above are what north_star asks to be reported, and small
-                "binding": {"bound": "valu_fp64", "achieved": (attempts * flop_per_attempt / elapsed / 1e12) if flop_per_attempt else None,
-                            "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                            "frac": (attempts * flop_per_attempt / elapsed / 1e12 / FP64_PEAK_TFLOPS) if flop_per_attempt else None,
-                            "kernel_time_frac": fp64_frac,
-                            "note": "algorithmic flops of every step attempt of one solve / wall time of the solve; kernel_time_frac: the same "
-                                    "flops / time inside the stepping kernels"},
-                "kernel": wl["kernel"], "avg_launch_ms": avg_launch_ms,
-                "launches_per_step": launches / args.steps,
-                # per kernel name, for a one-to-one check against the rocprofv3 --kernel-trace --stats rows
-                # (bulk, cooperative) launch PAIRS: exactly one launch of a pair works, its partner returns at once (~3 us).
-                # launches_per_step / avg_launch_ms are the working launches; *_incl_declined is what a kernel trace averages
-                # (rocprofv3 --stats counts the declined partner launches as calls of the same kernel)
-                "per_kernel": {
-                    "chunk_kernel_t": {"launches_per_step": (launches - coop_launches) / args.steps,
-                                       "avg_launch_ms": (kern_ms - coop_ms - (acc["decl_ms"] - acc["decl_coop_ms"])) / max(launches - coop_launches, 1),
-                                       "calls_per_step_incl_declined": (launches - coop_launches + acc["decl"] - acc["decl_coop"]) / args.steps,
-                                       "avg_call_ms_incl_declined": (kern_ms - coop_ms) / max(launches - coop_launches + acc["decl"] - acc["decl_coop"], 1)},
-                    "coop_chunk_kernel": {"launches_per_step": coop_launches / args.steps,
-                                          "avg_launch_ms": ((coop_ms - acc["decl_coop_ms"]) / coop_launches) if coop_launches else None,
-                                          "calls_per_step_incl_declined": (coop_launches + acc["decl_coop"]) / args.steps,
-                                          "avg_call_ms_incl_declined": (coop_ms / (coop_launches + acc["decl_coop"])) if (coop_launches + acc["decl_coop"]) else None},
-                },
-                "note": "state is device-resident: HBM traffic is per trajectory per launch, not per step; "
-                        "this fraction is informational, the binding resource is FP64 VALU issue (roofline_fp64)",
-            },
-            "roofline_fp64": {
-                "bound": "valu_fp64", "achieved": tflops, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": (tflops / FP64_PEAK_TFLOPS) if tflops is not None else None, "flop_per_attempt": flop_per_attempt,
-                "attempts_per_launch": attempts_per_launch,
-            },
-            "roofline_issue": issue,
-            "kernel_sources_sha256": sha_now,
         }
         if world > 1:
             res["rccl_ranks"] = dist.get_world_size()
+        if args.full:
+            res.update(roofline_figures(args, wl, prob, n_state, B, world, acc, attempts, elapsed, el_p, el_h))
         if weak is not None:
             res["weak"] = weak
-        if world > 1:
+        if world > 1 and args.full:
             # the builder's own single-GPU prediction of this curve, on the record next to the measured number
             # (every rank's shard timed alone on one MI355X; max over ranks = what the job takes, gather excluded)
             try:
                 pred = json.load(open(os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_strong_scaling_prediction.json")))
                 res["strong_scaling_prediction"] = {"source": f"profiles/{PROFILE_ROUND}_strong_scaling_prediction.json (tools/strong_scaling_prediction.py, strict mode, "
                                                               "one MI355X: every rank's shard timed alone, gather excluded)", "prediction": pred,
-                                                    "stale": pred.get("kernel_sources_sha256") != sha_now,
+                                                    "stale": pred.get("kernel_sources_sha256") != res["kernel_sources_sha256"],
                                                     "baseline_target": ">= 6x at 8 GPUs (BASELINE.json): out of reach for ONE 100k batch (the slowest "
                                                                        "trajectory's 702 sequential attempts do not shrink with the shard); the prediction "
                                                                        "file names the batch size that reaches it"}
@@ -385,12 +304,13 @@ def main():
                                          "step attempts (192 in the bulk kernel + 510 in the lane-cooperative tail kernel) "
                                          "do not shrink with the shard -- see DESIGN.md section 7")
         single = dist is None
+        secondary = args.full and not args.no_fast
         y0d, pd = torch.as_tensor(y0, device=dev), torch.as_tensor(p, device=dev)
-        if args.fp == "strict" and not args.no_fast and single and args.workload == "c2":   # single process only (it synchronises)
+        if args.fp == "strict" and secondary and single and args.workload == "c2":   # single process only (it synchronises)
             res["fma_fp_mode"] = fma_mode_numbers(ivp_amd, prob, t0, t1, y0d, pd, ctx, args, barrier_sync)
-        if not args.no_fast and single and args.workload == "c2":
+        if secondary and single and args.workload == "c2":
             res["pipelined"] = pipelined_numbers(ivp_amd, prob, t0, t1, y0d, pd, fp, args)
-        if single and args.workload in ("c2", "c3") and (args.output != "end" or not args.no_fast):
+        if single and args.workload in ("c2", "c3") and (args.output != "end" or secondary):
             modes = ["t_eval", "csr_log"] if args.output == "end" else (["t_eval", "csr_log", "dense", "events"] if args.output == "all" else [args.output])
             if args.workload != "c2":
                 modes = [m for m in modes if m != "events"]
@@ -402,7 +322,7 @@ def main():
                                     "ms_per_step": c["ms_per_solve"], "value": total_acc / (c["ms_per_solve"] * 1e-3), "unit": "steps/s",
                                     "records": c["records"], "bytes": c["bytes_written"], "vs_end_state": c["ms_per_solve"] / ms_per_step,
                                     "two_pass_ms_per_step": c["two_pass_ms_per_solve"], "passes": c["log_info"].get("passes")}
-        if not args.no_cpu_baseline and world == 1 and args.workload == "c2":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "c2":
             res["cpu_baseline"] = cpu_baseline(y0, p, t0, t1)
             res["accuracy"] = accuracy_vs_truth(ivp_amd, prob, mk_opts(0), ctx, dev)
         sys.stdout.flush()
@@ -412,6 +332,134 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_FIELDS = ("y_end", "t_end", "h_next", "status", "nfev", "nstep", "naccpt", "nrejct", "njev", "nlu")
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays a caller of the timed path receives, as <path>/<name>.npy in float64 (counters and status
+    words are exact there).  Every array's last axis is the trajectory; beyond DUMP_LIMIT_BYTES in all, the same fixed,
+    seeded sample of trajectories is taken from every array and its indices are written as sample_index.npy."""
+    arrays = {k: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[-1]
+    per_traj = sum(a.size // B for a in arrays.values()) * 8
+    if per_traj * B > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) // (per_traj + 8)   # + the index array, + room for the .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, k, replace=False))
+        arrays = {name: a[..., idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def roofline_figures(args, wl, prob, n_state, B, world, acc, attempts, elapsed, el_p, el_h):
+    """--full: the launch statistics of the instrumented pass turned into the roofline objects, beside the D2H wall time."""
+    launches, kern_ms, coop_ms, coop_launches = acc["launches"], acc["kern_ms"], acc["coop_ms"], acc["coop_launches"]
+    avg_launch_ms = kern_ms / max(launches, 1)
+    attempts_per_launch = attempts / max(launches, 1)
+    lanes_per_launch = acc["lane_launches"] / max(launches, 1)  # trajectories that load + store their state
+    flop_per_attempt = wl["flop_per_attempt"]
+    bytes_per_launch = lanes_per_launch * bytes_per_lane_launch(n_state, prob.n_params, args.workload)
+    gbs = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+    tflops = (attempts_per_launch * flop_per_attempt / (avg_launch_ms * 1e-3) / 1e12) if (avg_launch_ms > 0 and flop_per_attempt) else None
+    # PMC-derived figures come from committed profiles of this command (separate rocprofv3 --pmc passes: counters cannot be
+    # collected inside a timed run).  Each profile is stamped with the hash of the kernel sources it was taken on; a
+    # profile of OTHER kernels than the ones just timed is reported as stale and nothing is derived from it.
+    sha_now = kernel_sources_sha256()
+    traffic = traffic_src = None
+    traffic_stale = None
+    pmc_name = f"{PROFILE_ROUND}_pmc_hbm_bytes_per_launch_{args.fp}.json"
+    pmc = os.path.join(ROOT, "profiles", pmc_name)
+    if os.path.exists(pmc) and args.workload == "c2" and world == 1 and B == 100_000:
+        try:
+            j = json.load(open(pmc))
+            traffic_stale = j.get("kernel_sources_sha256") != sha_now
+            if not traffic_stale:
+                traffic = j.get("hbm_bytes_per_launch")
+            traffic_src = f"profiles/{pmc_name} (" + str(j.get("run", "rocprofv3 --pmc passes of tools/profile_c2.sh")) + \
+                          "): PMC counters of a separate profiled run of this command, not of this process" + \
+                          ("; STALE: taken on other kernel sources than this run's (hash mismatch), not used" if traffic_stale else "")
+        except Exception:
+            traffic = None
+    # VALU issue view of the dominant kernel: the thread-per-trajectory stepping kernel is bound by vector-instruction
+    # issue (one wave64 FP64 instruction per 4 cycles per SIMD at best), not by bytes or by counted flops (strict mode
+    # spends separate multiply and add instructions, 11 on a division, 18 on a square root).  Instructions per launch
+    # come from the committed SQ-counter profile of this command (profiles/<PROFILE_ROUND>_sq_counters_<workload>_<fp>.json,
+    # SQ_INSTS_VALU, tools/profile_sq.sh), the launch duration is this run's.
+    issue = None
+    sq_name = f"{PROFILE_ROUND}_sq_counters_{args.workload}_{args.fp}.json"
+    sqf = os.path.join(ROOT, "profiles", sq_name)
+    chunk_launches = launches - coop_launches
+    chunk_ms = (kern_ms - coop_ms) / max(chunk_launches, 1)
+    if os.path.exists(sqf) and world == 1 and B == wl["B"] and chunk_ms > 0:
+        try:
+            sq = json.load(open(sqf))
+            if sq.get("kernel_sources_sha256") != sha_now:
+                raise LookupError("stale")
+            ent = next(v for k, v in sq.items() if "chunk_kernel_t" in k and "coop" not in k)
+            valu = float(ent["mean_per_dispatch"]["SQ_INSTS_VALU"])
+            if "per_solve" in ent:   # instructions of a whole solve / this run's launches per solve: robust against a
+                valu = float(ent["per_solve"]["SQ_INSTS_VALU"]) / max(chunk_launches / args.steps, 1e-9)   # different cut into launches
+            peak = 256 * 4 * 2.4e9 / 4.0   # SIMDs x (clock / 4 cycles per wave64 instruction), at the 2.4 GHz peak clock
+            issue = {"bound": "valu_issue", "kernel": "chunk_kernel_t", "achieved": valu / (chunk_ms * 1e-3), "peak": peak,
+                     "unit": "wave-instructions/s", "frac": valu / (chunk_ms * 1e-3) / peak, "valu_instructions_per_launch": valu,
+                     "avg_launch_ms": chunk_ms,
+                     "source": f"profiles/{sq_name} (SQ_INSTS_VALU per launch, separate rocprofv3 --pmc "
+                               "run of this command) / this run's launch duration"}
+        except LookupError:
+            issue = {"bound": "valu_issue", "kernel": "chunk_kernel_t", "stale": True,
+                     "source": f"profiles/{sq_name}: taken on other kernel sources than this run's (hash mismatch), nothing derived"}
+        except Exception:
+            issue = None
+    fp64_frac = (tflops / FP64_PEAK_TFLOPS) if tflops is not None else None
+    return {
+        "wall_ms_with_d2h": el_h / args.steps * 1e3,
+        "instrumented_ms_per_step": el_p / args.steps * 1e3,
+        "timing_note": "value / ms_per_step: options.profile = 0 (no per-launch events); roofline launch durations come "
+                       "from a separate instrumented pass of the same K steps (instrumented_ms_per_step, this rank)",
+        "wave_lane_utilisation": attempts / acc["slots"] if acc["slots"] else None,
+        "roofline": {
+            "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+            # the resource that actually bounds this path (SURVEY.md section 8d): FP64 vector arithmetic, counted flops of the
+            # whole solve over its wall time -- the HBM figures above are what north_star asks to be reported, and small
+            "binding": {"bound": "valu_fp64", "achieved": (attempts * flop_per_attempt / elapsed / 1e12) if flop_per_attempt else None,
+                        "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": (attempts * flop_per_attempt / elapsed / 1e12 / FP64_PEAK_TFLOPS) if flop_per_attempt else None,
+                        "kernel_time_frac": fp64_frac,
+                        "note": "algorithmic flops of every step attempt of one solve / wall time of the solve; kernel_time_frac: the same "
+                                "flops / time inside the stepping kernels"},
+            "kernel": wl["kernel"], "avg_launch_ms": avg_launch_ms,
+            "launches_per_step": launches / args.steps,
+            # per kernel name, for a one-to-one check against the rocprofv3 --kernel-trace --stats rows
+            # (bulk, cooperative) launch PAIRS: exactly one launch of a pair works, its partner returns at once (~3 us).
+            # launches_per_step / avg_launch_ms are the working launches; *_incl_declined is what a kernel trace averages
+            # (rocprofv3 --stats counts the declined partner launches as calls of the same kernel)
+            "per_kernel": {
+                "chunk_kernel_t": {"launches_per_step": (launches - coop_launches) / args.steps,
+                                   "avg_launch_ms": (kern_ms - coop_ms - (acc["decl_ms"] - acc["decl_coop_ms"])) / max(launches - coop_launches, 1),
+                                   "calls_per_step_incl_declined": (launches - coop_launches + acc["decl"] - acc["decl_coop"]) / args.steps,
+                                   "avg_call_ms_incl_declined": (kern_ms - coop_ms) / max(launches - coop_launches + acc["decl"] - acc["decl_coop"], 1)},
+                "coop_chunk_kernel": {"launches_per_step": coop_launches / args.steps,
+                                      "avg_launch_ms": ((coop_ms - acc["decl_coop_ms"]) / coop_launches) if coop_launches else None,
+                                      "calls_per_step_incl_declined": (coop_launches + acc["decl_coop"]) / args.steps,
+                                      "avg_call_ms_incl_declined": (coop_ms / (coop_launches + acc["decl_coop"])) if (coop_launches + acc["decl_coop"]) else None},
+            },
+            "note": "state is device-resident: HBM traffic is per trajectory per launch, not per step; "
+                    "this fraction is informational, the binding resource is FP64 VALU issue (roofline_fp64)",
+        },
+        "roofline_fp64": {
+            "bound": "valu_fp64", "achieved": tflops, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": (tflops / FP64_PEAK_TFLOPS) if tflops is not None else None, "flop_per_attempt": flop_per_attempt,
+            "attempts_per_launch": attempts_per_launch,
+        },
+        "roofline_issue": issue,
+        "kernel_sources_sha256": sha_now,
+    }
 
 
 def fma_mode_numbers(ivp_amd, prob, t0, t1, y0d, pd, ctx, args, sync_all):

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_sha import kernel_sources_sha256   # noqa: E402
 
 src, out = sys.argv[1:3]
-solves = int(sys.argv[3]) if len(sys.argv) > 3 else None   # complete solves the profiled command ran (bench.py: 3 passes x (steps + warmup))
+solves = int(sys.argv[3]) if len(sys.argv) > 3 else None   # complete solves the profiled command ran (bench.py --full: 3 passes x (steps + warmup))
 acc = defaultdict(lambda: defaultdict(list))
 for r in csv.DictReader(open(src)):
     acc[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
