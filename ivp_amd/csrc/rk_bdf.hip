@@ -32,6 +32,7 @@
 #define IVP_NS ivp_bdf_strict
 #define IVP_LAUNCH_NAME ivp_launch_bdf_strict
 #endif
+#define IVP_RHS_INBAND 0
 #include "rk_core.h"
 #ifdef IVP_PHASE_PROF
 __device__ unsigned long long ivp_phase_ticks[16];

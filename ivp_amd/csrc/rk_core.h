@@ -144,6 +144,98 @@ IVP_HD double rs_signum(double v) { return v != v ? v : copysign(1.0, v); }  // 
 IVP_HD uint64_t d2u(double d) { return __builtin_bit_cast(uint64_t, d); }
 IVP_HD double u2d(uint64_t u) { return __builtin_bit_cast(double, u); }
 
+// ------------------------------------------------------------------------------------------------
+// IEEE division and square root on a guarded operand range, bit for bit what `/` and sqrt() give.
+//
+// On gfx950 the compiler expands n / d into
+//     D = v_div_scale(d, d, n);  N = v_div_scale(n, d, n)  [VCC]
+//     r = v_rcp(D);  t = fma(-D, r, 1);  r = fma(r, t, r);  t = fma(-D, r, 1);  r = fma(r, t, r)
+//     q = N * r;  e = fma(-D, q, N);  q = v_div_fmas(e, r, q)  [fma, scaled by 2^+-64 when VCC];  v_div_fixup(q, d, n)
+// and sqrt(x) into
+//     s = x < 2^-767;  X = v_ldexp(x, s ? 256 : 0);  y = v_rsq(X);  g = X * y;  h = y * 0.5;  r = fma(-h, g, 0.5)
+//     g = fma(g, r, g);  h = fma(h, r, h);  2 x { dd = fma(-g, g, X);  g = fma(dd, h, g) };  g = v_ldexp(g, s ? -128 : 0)
+//     return class(X) in {+-0, +inf} ? X : g
+// V_DIV_SCALE_F64 changes an operand or sets VCC only if n or d is 0 / denormal, d's reciprocal or the quotient is
+// denormal, n's biased exponent is <= 53 (|n| < 2^-969), or exp(n) - exp(d) >= 768.  So for |d| in [2^-300, 2^300] and a
+// numerator n that is 0, inf, NaN or has |n| in [2^-601, 2^423), the two scale steps return d and n unchanged with VCC = 0
+// (exponent difference <= 722, quotient >= 2^-901), v_div_fmas is a plain fma, and what remains is ivp_recip_inband (per
+// denominator, shareable by every numerator) plus ivp_div_inband (per numerator).  v_div_fixup is kept: its result for
+// n = +-0, +-inf or NaN does not depend on the quotient operand, so those numerators come out as the hardware gives them
+// (+-0 numerators are the rule: z = 0 on every planar orbit).  For x in [2^-767, inf) finite, both v_ldexp are by 0 and
+// the class select keeps g: ivp_sqrt_inband is the middle of the sequence.  Every kept instruction is the compiler's,
+// on the same operands (tests/test_gpu_inband_div_sqrt.py compares against the hardware `/` and sqrt bitwise).
+// Callers test the range once per right-hand-side evaluation for the whole wave (ivp_wave_all) and otherwise run the
+// plain expression.  On the host (tests/host_emul) the helpers are the plain operators.
+// ------------------------------------------------------------------------------------------------
+// IVP_RHS_INBAND = 0 (rk_bdf.hip) keeps the built-in right-hand sides on the plain operators: the BDF kernels already spill
+// and have no registers for the second body
+#ifndef IVP_RHS_INBAND
+#define IVP_RHS_INBAND 1
+#endif
+struct IvpRecip { double d, r; };   // a denominator and (device) its refined reciprocal
+IVP_HD IvpRecip ivp_recip_inband(double d)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double r = __builtin_amdgcn_rcp(d);
+    double t = __builtin_fma(-d, r, 1.0);
+    r = __builtin_fma(r, t, r);
+    t = __builtin_fma(-d, r, 1.0);
+    r = __builtin_fma(r, t, r);
+    return {d, r};
+#else
+    return {d, 0.0};
+#endif
+}
+IVP_HD double ivp_div_inband(double n, const IvpRecip &D)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double q = n * D.r;
+    const double e = __builtin_fma(-D.d, q, n);
+    return __builtin_amdgcn_div_fixup(__builtin_fma(e, D.r, q), D.d, n);
+#else
+    return n / D.d;
+#endif
+}
+IVP_HD double ivp_sqrt_inband(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    double dd = __builtin_fma(-g, g, x);
+    g = __builtin_fma(dd, h, g);
+    dd = __builtin_fma(-g, g, x);
+    return __builtin_fma(dd, h, g);
+#else
+    return sqrt(x);
+#endif
+}
+// the range of x = r^2 for which sqrt(x), and division by r^3 (|r^3| in [2^-300, 2^300]), take the helpers above;
+// NaN, inf and 0 fail it
+IVP_HD bool ivp_sq_inband(double x) { return (x >= 0x1p-200) & (x <= 0x1p200); }
+// a numerator of ivp_div_inband with a denominator of magnitude [2^-300, 2^300]: 0, inf, NaN or |n| in [2^-601, 2^423),
+// i.e. a frexp exponent in [-600, 423] (v_frexp_exp gives 0 for 0, inf and NaN)
+IVP_HD bool ivp_num_inband(double n)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)(__builtin_amdgcn_frexp_exp(n) + 600) < 1024u;
+#else
+    const double m = fabs(n);
+    return m == 0.0 || m != m || m == __builtin_inf() || (m >= 0x1p-601 && m < 0x1p423);
+#endif
+}
+// true in every active lane of the wave when `ok` is (a wave-uniform value: the branch on it is a scalar branch)
+IVP_HD bool ivp_wave_all(bool ok)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(!ok) == 0;
+#else
+    return ok;
+#endif
+}
+
 // Step-controller power x^e for x >= 0 (err^expo1, facold^beta, (0.01/der12)^(1/iord)):
 // exp2(e*log2 x) from IEEE +,-,*,/,fma,rint and bit moves only, ~2 ulp.  Replaces f64::powf
 // (dopri5.rs:351-353, dop853.rs:432-434, rk23.rs:289,303, mod.rs:276); deterministic on any IEEE
@@ -382,14 +474,31 @@ struct RhsCr3bp {    // examples/cr3bp.rs:23-36
         d[4] = fma(-g2, y, fma(-g1, y, fma(-2.0, vx, y)));
         d[5] = fma(-g2, z, fma(-g1, z, -0.0));
 #else
-        const double r1 = sqrt(a * a + y * y + z * z);
-        const double r2 = sqrt(b * b + y * y + z * z);
-        const double r13 = r1 * r1 * r1;  // powi(3)
-        const double r23 = r2 * r2 * r2;
+        // d[3] = x + 2.0 * vy - (1.0 - mu) * (x + mu) / r13 - mu * (x - 1.0 + mu) / r23
+        // d[4] = y - 2.0 * vx - (1.0 - mu) * y / r13 - mu * y / r23
+        // d[5] = -(1.0 - mu) * z / r13 - mu * z / r23
+        const double s1 = a * a + y * y + z * z, s2 = b * b + y * y + z * z;
+        const double c1 = 1.0 - mu;
+        const double n3a = c1 * a, n3b = mu * b, n4a = c1 * y, n4b = mu * y, n5a = -c1 * z, n5b = mu * z;
+        const double l3 = x + 2.0 * vy, l4 = y - 2.0 * vx;
         d[0] = vx; d[1] = vy; d[2] = vz;
-        d[3] = x + 2.0 * vy - (1.0 - mu) * (x + mu) / r13 - mu * (x - 1.0 + mu) / r23;
-        d[4] = y - 2.0 * vx - (1.0 - mu) * y / r13 - mu * y / r23;
-        d[5] = -(1.0 - mu) * z / r13 - mu * z / r23;
+        // the whole wave in range (see ivp_recip_inband): one refined reciprocal per primary serves its three numerators
+        // (& rather than &&: straight-line compares, no exec-mask branches)
+        if (IVP_RHS_INBAND && ivp_wave_all(ivp_sq_inband(s1) & ivp_sq_inband(s2) & ivp_num_inband(n3a) & ivp_num_inband(n3b) &
+                         ivp_num_inband(n4a) & ivp_num_inband(n4b) & ivp_num_inband(n5a) & ivp_num_inband(n5b))) {
+            const double r1 = ivp_sqrt_inband(s1), r2 = ivp_sqrt_inband(s2);
+            const IvpRecip i13 = ivp_recip_inband(r1 * r1 * r1), i23 = ivp_recip_inband(r2 * r2 * r2);
+            d[3] = l3 - ivp_div_inband(n3a, i13) - ivp_div_inband(n3b, i23);
+            d[4] = l4 - ivp_div_inband(n4a, i13) - ivp_div_inband(n4b, i23);
+            d[5] = ivp_div_inband(n5a, i13) - ivp_div_inband(n5b, i23);
+        } else {   // a collision orbit, far away, tiny numerators, NaN / inf: the plain operators
+            const double r1 = sqrt(s1), r2 = sqrt(s2);
+            const double r13 = r1 * r1 * r1;  // powi(3)
+            const double r23 = r2 * r2 * r2;
+            d[3] = l3 - n3a / r13 - n3b / r23;
+            d[4] = l4 - n4a / r13 - n4b / r23;
+            d[5] = n5a / r13 - n5b / r23;
+        }
 #endif
     }
 #if defined(__HIPCC__)
