@@ -393,6 +393,77 @@ int ivp_batch_solve_logged(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
 void ivp_step_log_free(ivp_step_log_t *log);
 
 /*
+ * Every trajectory's complete ContinuousOutput (Solution.sol / sol_many, src/solve/cont.rs:9-153, solution.rs:25-69) in
+ * CSR form: the dense-output segments of B solve_ivp(.., Options.dense_output = true) calls without a cap.
+ *
+ *     trajectory b's k-th segment is record q = offsets[b] + k:  xold[q], h[q],
+ *     cont[q * (ncoef * n) + ..]   ncoef = Method::coeffs_per_state; RK: [coef][component], BDF: per-state blocks
+ *                                  [D0, D1..D5, order] (cont.rs:44-51)
+ * exactly the segments the reference pushes (src/solve/solout.rs:141-146), in integration order, and the single constant
+ * segment (h = 1e-15) of a zero-length interval.  The result takes sum(n_seg) x (2 + ncoef n) doubles.
+ *
+ * How: a counting solve (the solve itself: `out` receives every member as in ivp_batch_solve_device -- t_eval samples,
+ * events, a bounded step log of opt->max_log records -- and n_seg, if given, the counts), an exclusive scan of the counts
+ * into `offsets`, then the segments: from the counting solve's own block when every run fits opt->max_log (passes = 1),
+ * else from a filling solve over trajectory ranges whose bounded blocks fit half of the free device memory, packed into
+ * the CSR arrays (passes = 2).  out->seg_cont / seg_xold / seg_h must be NULL; opt->dense_output is implied.
+ * PEAK device memory: the result plus that staging block, [max n_seg of the range][2 + ncoef n] doubles per trajectory
+ * of a range (reported in staging_bytes; BASELINE C2: about 3x the result, as much as the bounded dense solve takes);
+ * the environment variable IVP_DENSE_STAGING_BYTES caps the block, at the price of one filling solve per range.
+ *
+ * ivp_dense_log_t -- who owns what (as ivp_step_log_t):
+ *   offsets   [B + 1], ALWAYS the caller's (device memory for the device form, host memory for the host form)
+ *   cont, xold, h   the caller's buffers of `capacity` records, or all NULL: the library allocates exactly `total`
+ *             records (hipMalloc on the context's device, malloc for the host form), sets owned = 1, and the caller
+ *             releases them with ivp_dense_log_free()
+ * Returns IVP_ERR_LOG_CAPACITY (with total and offsets set) when the caller's buffers are too small, IVP_ERR_HIP with a
+ * message when the device has not the memory for the result or the staging: never a truncated log.
+ */
+typedef struct {
+    uint64_t *offsets;
+    double *cont;
+    double *xold;
+    double *h;
+    uint64_t capacity;
+    /* ---- out ---- */
+    int32_t owned;            /* 1: cont / xold / h were allocated by the library                                   */
+    int32_t device;           /* HIP device of owned device memory, -1 for host memory                             */
+    uint32_t passes;          /* integrations it took: 1 (every run fitted the counting solve's block) or 2         */
+    uint32_t ncoef_n;         /* doubles per record of cont                                                        */
+    uint64_t total;           /* number of segments = offsets[B]                                                   */
+    uint64_t staging_bytes;   /* largest bounded segment block a solve of this call wrote into                     */
+} ivp_dense_log_t;
+
+int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0,
+                                 const double *params, const double *t0, size_t t0_len, const double *t1,
+                                 size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out,
+                                 ivp_dense_log_t *dense, void *hip_stream);
+/* host pointers throughout (arguments as ivp_batch_solve; dense->offsets / cont / xold / h are host memory) */
+int ivp_batch_solve_dense(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                          const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                          ivp_batch_result_t *out, ivp_dense_log_t *dense);
+/* an owned device log (owned = 1, device >= 0) into the caller's device buffers of dense->total records, on hip_stream;
+ * the owned memory is released and dense then points at the caller's buffers (owned = 0) */
+int ivp_dense_log_fetch_device(ivp_dense_log_t *dense, double *cont, double *xold, double *h, void *hip_stream);
+void ivp_dense_log_free(ivp_dense_log_t *dense);
+
+/*
+ * ContinuousOutput::evaluate (extrapolate == 0) / evaluate_extrapolate (extrapolate != 0), src/solve/cont.rs:104-153, of
+ * every trajectory of a CSR dense log at query times, on the device (all arrays device memory, enqueued on hip_stream).
+ *   t_offsets == NULL: one grid t[m] shared by the batch; y [m][n][B] (the SoA layout of a shared t_eval), found [m][B]
+ *   t_offsets != NULL: [B + 1] offsets of per-trajectory grids concatenated in t[m], m = t_offsets[B]; y [m][n]
+ *                      (time-major, the layout of per-trajectory t_eval), found [m]
+ * found: 0 = no segment (y = NaN), 1 = inside a segment, 2 = extrapolated.  The segment is the reference's choice
+ * (the first one with left - 1e-12 <= t <= right + 1e-12), found by binary search: a trajectory's run must be monotone
+ * in its integration direction, as every run ivp_batch_solve_dense* writes is.  fp_mode: the interpolant of the
+ * stepping kernels of that arithmetic (IVP_FP_STRICT: the crate's association).
+ */
+int ivp_dense_eval_device(ivp_ctx_t *ctx, int32_t method, int32_t n, int32_t fp_mode, size_t B, const uint64_t *offsets,
+                          const double *cont, const double *xold, const double *h, const double *t,
+                          const uint64_t *t_offsets, uint64_t m, int32_t extrapolate, double *y, int32_t *found,
+                          void *hip_stream);
+
+/*
  * One batch over several devices.  The reference has no parallelism (a batch is B back-to-back solve_ivp() calls,
  * src/solve/solve_ivp.rs:99-313, with no coupling between them), so the batch shards by trajectory range: shard k is
  * integrated by its own context on its own device with no communication, and the only data movement is the final

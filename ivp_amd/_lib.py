@@ -58,6 +58,13 @@ class StepLogT(C.Structure):
                 ("pool_bytes", C.c_uint64), ("pool_used_bytes", C.c_uint64), ("page_slots", C.c_uint32)]
 
 
+class DenseLogT(C.Structure):
+    """ivp_dense_log_t: every trajectory's ContinuousOutput segments as a CSR log (ivp_batch_solve_dense*())."""
+    _fields_ = [("offsets", C.c_void_p), ("cont", C.c_void_p), ("xold", C.c_void_p), ("h", C.c_void_p), ("capacity", C.c_uint64),
+                ("owned", C.c_int32), ("device", C.c_int32), ("passes", C.c_uint32), ("ncoef_n", C.c_uint32), ("total", C.c_uint64),
+                ("staging_bytes", C.c_uint64)]
+
+
 class ShardT(C.Structure):
     """ivp_shard_t: trajectories [first, first + count) of a batch, resident on ctx's device (SoA stride count)."""
     _fields_ = [("ctx", C.c_void_p), ("first", C.c_size_t), ("count", C.c_size_t),
@@ -82,6 +89,7 @@ EXPORTS = (
     "ivp_batch_solve_device", "ivp_batch_submit_device", "ivp_batch_poll", "ivp_batch_wait", "ivp_batch_solve_multi", "ivp_batch_solve_multi_host",
     "ivp_rhs_compile", "ivp_rhs_compile_events", "ivp_rhs_compile_ex", "ivp_rhs_free",
     "ivp_batch_solve_logged", "ivp_batch_solve_logged_device", "ivp_step_log_fetch_device", "ivp_step_log_free", "ivp_batch_solve_logged_multi", "ivp_step_log_fetch_multi",
+    "ivp_batch_solve_dense_device", "ivp_batch_solve_dense", "ivp_dense_log_fetch_device", "ivp_dense_log_free", "ivp_dense_eval_device",
 )
 
 ERRORS = {
@@ -166,6 +174,17 @@ def load():
                                                C.c_int32, C.POINTER(BatchResultT), C.POINTER(StepLogT)]
     L.ivp_step_log_fetch_multi.restype = C.c_int
     L.ivp_step_log_fetch_multi.argtypes = [C.POINTER(ShardT), C.c_int32, C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT), C.c_int32, C.POINTER(StepLogT)]
+    L.ivp_batch_solve_dense_device.restype = C.c_int
+    L.ivp_batch_solve_dense_device.argtypes = solve_args + [C.POINTER(DenseLogT), C.c_void_p]
+    L.ivp_batch_solve_dense.restype = C.c_int
+    L.ivp_batch_solve_dense.argtypes = solve_args + [C.POINTER(DenseLogT)]
+    L.ivp_dense_log_fetch_device.restype = C.c_int
+    L.ivp_dense_log_fetch_device.argtypes = [C.POINTER(DenseLogT), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ivp_dense_log_free.restype = None
+    L.ivp_dense_log_free.argtypes = [C.POINTER(DenseLogT)]
+    L.ivp_dense_eval_device.restype = C.c_int
+    L.ivp_dense_eval_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ivp_rhs_compile.restype = C.c_int
     L.ivp_rhs_compile.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.ivp_rhs_compile_events.restype = C.c_int

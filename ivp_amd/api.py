@@ -685,6 +685,10 @@ class BatchSolution:
     event_overflow: bool = False  # some trajectory detected more occurrences of an event than max_events could store
     log_info: dict = field(default_factory=dict)   # solve_ivp_batch_logged: passes (1 = page pool, 2 = counted fill pass), pages, ...
     _log_buffers: object = None   # the full-capacity t / y buffers behind t_log / y_log (reused through `out=`)
+    # CSR dense log (solve_ivp_batch_dense): [B+1] segment offsets; seg_cont is then [total, ncoef n], seg_xold / seg_h [total]
+    seg_offsets: object = None
+    dense: object = None          # solve_ivp_batch_dense: BatchContinuousOutput over those segments (Solution.sol of every trajectory)
+    dense_info: dict = field(default_factory=dict)   # solve_ivp_batch_dense: passes, segments, bytes, staging_bytes
 
     def eval_of(self, b: int):
         """(index into trajectory b's own t_eval grid, y) of its emitted samples (per-trajectory grids); index -1 marks the
@@ -766,7 +770,7 @@ class PendingBatch:
 
 
 def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                    out: BatchSolution = None, wait: bool = True, _steplog=None):
+                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None):
     """B independent ``solve_ivp(f, t0[b], t1[b], y0[:, b], options)`` calls on the GPU.
 
     ``y0``: ``[n, B]`` float64, numpy (host path: staged through the library) or a CUDA torch tensor
@@ -903,7 +907,9 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         res.t_log = xp_zeros((ml, B), f64)
         res.y_log = xp_zeros((ml, n, B), f64)
         res.n_log = xp_zeros((B,), u32)
-    if options.dense_output and ml > 0 and res.seg_cont is None:
+    if _dense is not None and res.n_seg is None:   # solve_ivp_batch_dense: the segments go to the CSR log, the counts come back
+        res.n_seg = xp_zeros((B,), u32)
+    if options.dense_output and ml > 0 and res.seg_cont is None and _dense is None:
         res.seg_cont = xp_zeros((ml, nc, B), f64)
         res.seg_xold = xp_zeros((ml, B), f64)
         res.seg_h = xp_zeros((ml, B), f64)
@@ -942,7 +948,14 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         if rc != 0:
             raise ConfigError(rc, ctx.last_error())
         return PendingBatch(ctx, res, bool(options.profile), keep + [y0, params, t0a, t1a, copt, r])
-    if _steplog is not None:   # solve_ivp_batch_logged: ONE integration that also records every accepted step (page pool + gather)
+    if _dense is not None:   # solve_ivp_batch_dense: counting solve + scan + the segments as a CSR log
+        import torch
+        if not on_device:
+            raise ValueError("the CSR dense log takes device arrays")
+        stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
+        rc = ctx.lib.ivp_batch_solve_dense_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                  ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_dense), stream)
+    elif _steplog is not None:   # solve_ivp_batch_logged: ONE integration that also records every accepted step (page pool + gather)
         import torch
         if not on_device:
             raise ValueError("the one-pass step log takes device arrays")
@@ -1051,6 +1064,125 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
     res.t_log, res.y_log = bufs[0][:total], bufs[1][:total]
     res.log_info = {"passes": int(sl.passes), "records": total, "page_slots": int(sl.page_slots), "pool_bytes": int(sl.pool_bytes),
                     "pool_used_bytes": int(sl.pool_used_bytes), "form": "page pool + gather (one integration)" if sl.passes == 1 else "the pool ran dry: second integration"}
+    return res
+
+
+class BatchContinuousOutput:
+    """``Solution.sol`` of every trajectory of a batch (src/solve/cont.rs:9-153, solution.rs:25-69): the CSR dense log of
+    ``solve_ivp_batch_dense``, kept on the device and evaluated there (``ivp_dense_eval_device``: a binary search over the
+    trajectory's run for the segment the reference's linear scan finds, then the stepping kernels' own interpolant --
+    strict mode is the crate's association, bit for bit the host ``ContinuousOutput``)."""
+
+    def __init__(self, method: Method, n_states: int, offsets, cont, xold, h, fp_mode, ctx: "Context"):
+        self.method, self.n_states, self.fp_mode, self.ctx = Method(int(method)), int(n_states), FpMode(int(fp_mode)), ctx
+        self.offsets, self.cont, self.xold, self.h = offsets, cont, xold, h
+
+    @property
+    def batch(self) -> int:
+        return int(self.offsets.shape[0]) - 1
+
+    def of(self, b: int) -> ContinuousOutput:
+        """Trajectory b's ContinuousOutput on the host -- the one a single ``solve_ivp(.., dense_output=True)`` builds."""
+        lo, hi = int(self.offsets[b]), int(self.offsets[b + 1])
+        return ContinuousOutput(self.method, self.n_states, self.cont[lo:hi].cpu().numpy(), self.xold[lo:hi].cpu().numpy(),
+                                self.h[lo:hi].cpu().numpy())
+
+    def t_span(self):
+        """``ContinuousOutput::t_span`` of every trajectory: (start [B], end [B]) device tensors, NaN where a run is empty."""
+        import torch
+        lo, hi = self.offsets[:-1], self.offsets[1:]
+        nan = torch.full((self.batch,), float("nan"), dtype=torch.float64, device=self.offsets.device)
+        total = int(self.xold.shape[0])
+        if total == 0:
+            return nan, nan.clone()
+        empty = hi == lo
+        first, last = torch.clamp(lo, max=total - 1), torch.clamp(hi - 1, min=0, max=total - 1)
+        return torch.where(empty, nan, self.xold[first]), torch.where(empty, nan, self.xold[last] + self.h[last])
+
+    def __call__(self, t, extrapolate: bool = False):
+        """y(t) of every trajectory, evaluated on the device.  Returns (y, found):
+        * ``t`` a scalar: y [n, B], found [B];  a 1-D grid shared by the batch: y [m, n, B], found [m, B];
+        * ``t`` a list of B 1-D grids (one per trajectory): y [total, n] (time-major), found [total].
+        found: 0 = no segment (y = NaN), 1 = inside a segment, 2 = extrapolated (``extrapolate=True``:
+        ``evaluate_extrapolate``, cont.rs:122-153)."""
+        import torch
+        dev = self.offsets.device
+        B, n = self.batch, self.n_states
+        per_traj = isinstance(t, (list, tuple)) and len(t) > 0 and all(getattr(g, "ndim", np.ndim(g)) == 1 for g in t)
+        scalar = False
+        if per_traj:
+            if len(t) != B:
+                raise ValueError(f"one grid per trajectory ({B}), got {len(t)}")
+            grids = [torch.as_tensor(g, dtype=torch.float64, device=dev).reshape(-1) for g in t]
+            q_off = torch.zeros(B + 1, dtype=torch.int64)
+            torch.cumsum(torch.tensor([g.numel() for g in grids], dtype=torch.int64), 0, out=q_off[1:])
+            q_off = q_off.to(dev)
+            tt = torch.cat(grids).contiguous()
+            m = int(tt.numel())
+            y = torch.empty((m, n), dtype=torch.float64, device=dev)
+            found = torch.empty(m, dtype=torch.int32, device=dev)
+        else:
+            scalar = (t.ndim == 0) if _is_torch(t) else np.ndim(t) == 0
+            tt = torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+            q_off = None
+            m = int(tt.numel())
+            y = torch.empty((m, n, B), dtype=torch.float64, device=dev)
+            found = torch.empty((m, B), dtype=torch.int32, device=dev)
+        if m and B:
+            vp = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            rc = self.ctx.lib.ivp_dense_eval_device(self.ctx.handle, int(self.method), n, int(self.fp_mode), B, vp(self.offsets), vp(self.cont),
+                                                    vp(self.xold), vp(self.h), vp(tt), vp(q_off), m, int(bool(extrapolate)), vp(y), vp(found), stream)
+            if rc != 0:
+                raise ConfigError(rc, self.ctx.last_error())
+        if scalar:
+            return y[0], found[0]
+        return y, found
+
+
+def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None) -> BatchSolution:
+    """B independent ``solve_ivp(.., Options(dense_output=True))`` calls with EVERY trajectory's complete ContinuousOutput
+    (src/solve/cont.rs:9-153), not capped at ``max_log``: the segments come back as a CSR log on the device.
+
+    The members of the result are those of ``solve_ivp_batch`` with the same options (t_eval samples, events, a bounded step
+    log of ``max_log`` records), plus ``seg_offsets`` [B+1], ``seg_cont`` [total, ncoef n] (RK: [coef][component], BDF:
+    per-state blocks [D0, D1..D5, order]), ``seg_xold`` / ``seg_h`` [total], ``n_seg`` [B], ``dense_info`` and ``dense``, a
+    ``BatchContinuousOutput`` that evaluates every trajectory's y(t) on the device.  The result takes sum(n_seg) x
+    (2 + ncoef n) doubles.  How (``ivp_batch_solve_dense_device``): a counting solve, an exclusive scan of the counts, then
+    the segments -- from the counting solve itself when every run fits ``max_log``, else from a filling solve
+    (``dense_info["passes"]`` = 2) whose unchanged stepping kernels write a bounded staging block of
+    [max n_seg][2 + ncoef n] doubles per trajectory that is then packed into the CSR arrays.  PEAK device memory is the
+    result plus that block (``dense_info["staging_bytes"]``; BASELINE C2: about 3x the result), and the library-owned
+    result is copied once into the returned tensors; ``IVP_DENSE_STAGING_BYTES`` caps the block at the price of one
+    filling solve per trajectory range."""
+    import torch
+    options = options or Options()
+    ctx = ctx or default_context(y0.device.index or 0 if _is_torch(y0) else 0)
+    dev = y0.device if _is_torch(y0) else torch.device("cuda", ctx.device)
+    to_dev = lambda a: None if a is None else (a if _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev))
+    y0d, pd = to_dev(y0), to_dev(params)
+    tt = lambda v: v if (np.ndim(v) == 0 and not _is_torch(v)) else to_dev(v)
+    t0d, t1d = tt(t0), tt(t1)
+    B = int(y0d.shape[1])
+    dl = _lib.DenseLogT()
+    offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    dl.offsets = offsets.data_ptr()
+    try:
+        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**{**options.__dict__, "dense_output": True}), ctx, _dense=dl)
+        total, nc = int(dl.total), int(dl.ncoef_n)
+        cont = torch.empty((max(total, 1), nc), dtype=torch.float64, device=dev)
+        xold = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        h = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = ctx.lib.ivp_dense_log_fetch_device(C.byref(dl), C.c_void_p(cont.data_ptr()), C.c_void_p(xold.data_ptr()), C.c_void_p(h.data_ptr()), stream)
+        if rc != 0:
+            raise ConfigError(rc, "ivp_dense_log_fetch_device")
+    finally:
+        ctx.lib.ivp_dense_log_free(C.byref(dl))   # owned device memory the fetch did not take over (an error on the way)
+    res.seg_offsets = offsets
+    res.seg_cont, res.seg_xold, res.seg_h = cont[:total], xold[:total], h[:total]
+    res.dense_info = {"passes": int(dl.passes), "segments": total, "bytes": total * (nc + 2) * 8, "staging_bytes": int(dl.staging_bytes)}
+    res.dense = BatchContinuousOutput(options.method_enum, int(y0d.shape[0]), offsets, res.seg_cont, res.seg_xold, res.seg_h, options.fp_mode, ctx)
     return res
 
 

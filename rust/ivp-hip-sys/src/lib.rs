@@ -157,6 +157,24 @@ pub struct ivp_step_log_t {
     pub page_slots: u32,
 }
 
+/// Every trajectory's ContinuousOutput segments as a CSR log (src/solve/cont.rs:9-153): record offsets[b] + k holds
+/// xold, h and ncoef_n coefficients; cont / xold / h null on entry = allocated by the library (`owned` = 1; release with
+/// `ivp_dense_log_free`).
+#[repr(C)]
+pub struct ivp_dense_log_t {
+    pub offsets: *mut u64,
+    pub cont: *mut f64,
+    pub xold: *mut f64,
+    pub h: *mut f64,
+    pub capacity: u64,
+    pub owned: i32,
+    pub device: i32,
+    pub passes: u32,
+    pub ncoef_n: u32,
+    pub total: u64,
+    pub staging_bytes: u64,
+}
+
 pub enum ivp_ctx_t {}
 
 /// trajectories [first, first + count) of a batch, resident on ctx's device (SoA stride `count`)
@@ -210,6 +228,20 @@ extern "C" {
                                   t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
                                   out: *mut ivp_batch_result_t, log: *mut ivp_step_log_t) -> c_int;
     pub fn ivp_step_log_free(log: *mut ivp_step_log_t);
+    // Solution.sol of every trajectory: the dense-output segments in CSR form, and their evaluation on the device
+    pub fn ivp_batch_solve_dense_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64,
+                                        params: *const f64, t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize,
+                                        opt: *const ivp_options_t, out: *mut ivp_batch_result_t, dense: *mut ivp_dense_log_t,
+                                        hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_batch_solve_dense(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                 t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                 out: *mut ivp_batch_result_t, dense: *mut ivp_dense_log_t) -> c_int;
+    pub fn ivp_dense_log_fetch_device(dense: *mut ivp_dense_log_t, cont: *mut f64, xold: *mut f64, h: *mut f64,
+                                      hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_dense_log_free(dense: *mut ivp_dense_log_t);
+    pub fn ivp_dense_eval_device(ctx: *mut ivp_ctx_t, method: i32, n: i32, fp_mode: i32, b: usize, offsets: *const u64,
+                                 cont: *const f64, xold: *const f64, h: *const f64, t: *const f64, t_offsets: *const u64,
+                                 m: u64, extrapolate: i32, y: *mut f64, found: *mut i32, hip_stream: *mut c_void) -> c_int;
     // one batch over several devices: N contexts driven by this thread, shards gathered by peer copies (xGMI)
     pub fn ivp_batch_solve_multi(shards: *mut ivp_shard_t, n_shards: i32, prob: *const ivp_problem_t, b: usize,
                                  opt: *const ivp_options_t, gather_device: i32, gathered: *mut ivp_batch_result_t) -> c_int;
