@@ -7,10 +7,15 @@
 // (n <= 8): every lane holds one component of y and of every k-stage, so the stage combinations, the error estimate
 // and the state update are one component's worth of work per lane instead of n.
 //
-// Data movement inside a group is DPP (v_mov_b32 with a lane-select modifier: ~12 cycles per hop, two movs per
-// double), not ds_bpermute (60-70 cycles per hop through the LDS crossbar):
-//   quad_bcast<i>   lane i of every quad (4 lanes) to the whole quad          quad_perm:[i,i,i,i]
+// Data movement inside a group is DPP (v_mov with a lane-select modifier: ~12 cycles per hop), not ds_bpermute (60-70
+// cycles per hop through the LDS crossbar):
+//   quad_bcast<i>   lane i of every quad (4 lanes) to the whole quad          quad_perm:[i,i,i,i]      2 x v_mov_b32_dpp
 //   lo_to_hi / hi_to_lo   lanes 0..3 of a group to lanes 4..7 and back        row_shr:4 / row_shl:4 with a bank mask
+//   lo_to_hi_only   the same hop where only lanes 4..7 are read afterwards: every lane is written (bound_ctrl), so the
+//                   result is a fresh register and no copy has to protect the source
+//   grp_bcast<i>    lane i of every group to its eight lanes                  row_newbcast             2 x v_mov_b64_dpp
+// gfx950 moves a whole double with one v_mov_b64_dpp, but only for row_newbcast (lane n of each 16-lane row to the lanes the
+// bank mask selects); tools/ubench_dpp64.hip measures it against the 32-bit pair.
 // The two quads of a group are used as two "halves" that run the SAME instruction stream on different operands
 // wherever the reference has two independent evaluations of one expression shape:
 //   * the step controller's two powers err^expo1 and facold^beta (NormOps::pow2): one ivp_pow per lane;
@@ -19,8 +24,8 @@
 // A functor may also choose which lane holds which component (coop_lane_of) so that those exchanges are single hops.
 // Generic functors (incl. hiprtc user code) gather the whole stage vector and evaluate R::ode redundantly.
 //
-// The weighted error norm adds the n squared terms in index order (the reference's left-to-right sum) walking
-// through the quads, and ends up identical in the eight lanes, so the controller scalars agree across the group and
+// The weighted error norm adds the n squared terms in index order (the reference's left-to-right sum), every term
+// broadcast to the whole group, and is identical in the eight lanes, so the controller scalars agree across the group and
 // accept/reject stays group-uniform.
 //
 // Like the wave-per-trajectory kernels (rk_group.h) this is not a second integrator: the attempt bodies and the device
@@ -37,11 +42,12 @@ namespace IVP_NS {
 // ---- DPP moves of doubles -------------------------------------------------------------------------------------
 // CTRL: dpp_ctrl (quad_perm 0x00..0xFF, row_shl:n 0x100+n, row_shr:n 0x110+n); BANK: which quads of a 16-lane row are
 // written (bit q = lanes 4q..4q+3); unwritten lanes keep `old`.
-template <int CTRL, int BANK>
+template <int CTRL, int BANK, bool ALL = (BANK == 0xF && CTRL < 0x100)>
 __device__ __forceinline__ double dpp_f64(double old, double src)
 {
-    // a full-width quad_perm writes every lane from a valid source: bound_ctrl tells the compiler that `old` is dead
-    constexpr bool kAll = BANK == 0xF && CTRL < 0x100;
+    // ALL: every lane is written (a full-width quad_perm has a valid source for each; a full-width row shift writes 0 where
+    // it has none): bound_ctrl tells the compiler that `old` is dead
+    constexpr bool kAll = ALL;
     const uint64_t o = d2u(old), s = d2u(src);
     const int lo = __builtin_amdgcn_update_dpp((int)(uint32_t)o, (int)(uint32_t)s, CTRL, 0xF, BANK, kAll);
     const int hi = __builtin_amdgcn_update_dpp((int)(uint32_t)(o >> 32), (int)(uint32_t)(s >> 32), CTRL, 0xF, BANK, kAll);
@@ -53,14 +59,19 @@ __device__ __forceinline__ double quad_bcast(double v) { return dpp_f64<I * 0x55
 __device__ __forceinline__ double lo_to_hi(double old, double src) { return dpp_f64<0x114, 0xA>(old, src); }
 // lanes 0..3 of every group take `src` of the lane four above; lanes 4..7 keep `old`
 __device__ __forceinline__ double hi_to_lo(double old, double src) { return dpp_f64<0x104, 0x5>(old, src); }
-// lane I (0..7) of every group to its eight lanes
+// lanes 4..7 of every group take `src` of the lane four below; lanes 0..3 hold nothing of use (0 in the first group of a row,
+// the neighbouring group's upper lanes in the second) and must not be read
+__device__ __forceinline__ double lo_to_hi_only(double src) { return dpp_f64<0x114, 0xF, true>(0.0, src); }
+// lane I (0..7) of every group to its eight lanes, in two halves: lane I of the row's first group to the whole row (every
+// lane written: no `old`), then lane 8 + I, the same lane of its second group, to lanes 8..15.  A DPP mov must not read a
+// register -- `old` included -- within two instructions of the one that wrote it (the compiler fills the gap with s_nop, an
+// issue slot each for a lone wave), so callers with several broadcasts issue all first halves, then all second halves.
 template <int I>
-__device__ __forceinline__ double grp_bcast(double v)
-{
-    const double t = quad_bcast<(I & 3)>(v);
-    if constexpr (I < 4) return lo_to_hi(t, t);
-    else return hi_to_lo(t, t);
-}
+__device__ __forceinline__ double grp_bcast_row(double v) { return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + I, 0xF, 0xF, true); }      // row_newbcast:I
+template <int I>
+__device__ __forceinline__ double grp_bcast_fix(double t, double v) { return __builtin_amdgcn_update_dpp(t, v, 0x158 + I, 0xF, 0xC, false); }   // row_newbcast:8+I, lanes 8..15
+template <int I>
+__device__ __forceinline__ double grp_bcast(double v) { return grp_bcast_fix<I>(grp_bcast_row<I>(v), v); }
 
 // ---- which lane of the group holds which component --------------------------------------------------------------
 template <class R, class = void>
@@ -78,6 +89,18 @@ __device__ __forceinline__ uint32_t coop_comp()
     return c;
 }
 
+// f(CoopIdx<0>), ..., f(CoopIdx<N - 1>): a loop whose index is a compile-time constant (a template argument of the DPP movs)
+template <int I>
+struct CoopIdx { constexpr operator int() const { return I; } };
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void coop_for(const F &f)
+{
+    if constexpr (I < N) {
+        f(CoopIdx<I>{});
+        coop_for<N, I + 1>(f);
+    }
+}
+
 template <int N>
 __device__ __forceinline__ double coop_select(const double (&v)[N], uint32_t c)
 {
@@ -92,41 +115,27 @@ __device__ __forceinline__ double coop_select(const double (&v)[N], uint32_t c)
     }
     return s;
 }
-template <class R, int I>
-__device__ __forceinline__ void coop_gather_from(double v, double (&out)[R::N])
-{
-    if constexpr (I < R::N) {
-        out[I] = grp_bcast<CoopLayout<R>::lane_of(I)>(v);
-        coop_gather_from<R, I + 1>(v, out);
-    }
-}
 // the whole vector, in component order, in every lane of the group
 template <class R>
-__device__ __forceinline__ void coop_gather(double v, double (&out)[R::N]) { coop_gather_from<R, 0>(v, out); }
-
-// sum_{i<N} term_i in index order (0.0 + t0 + t1 + ...); term_i lives in lane lane_of(i).  The running sum walks
-// through the quads in component order (valid in the quad that holds component i) and is copied to the other quad at
-// the end: 2 hops per term + 2 per quad change instead of 4 per term.
-template <class R, int I>
-__device__ __forceinline__ double coop_sum_from(double s, double t)
+__device__ __forceinline__ void coop_gather(double v, double (&out)[R::N])
 {
-    using LAY = CoopLayout<R>;
-    if constexpr (I == R::N) {
-        constexpr int q = LAY::lane_of(R::N - 1) >> 2;
-        if constexpr (q == 1) return hi_to_lo(s, s);
-        else return lo_to_hi(s, s);
-    } else {
-        constexpr int li = LAY::lane_of(I), qi = li >> 2;
-        if constexpr (I > 0) {
-            constexpr int qp = LAY::lane_of(I - 1) >> 2;
-            if constexpr (qp != qi) s = (qi == 1) ? lo_to_hi(s, s) : hi_to_lo(s, s);
-        }
-        s += quad_bcast<(li & 3)>(t);
-        return coop_sum_from<R, I + 1>(s, t);
-    }
+    coop_for<R::N>([&](auto i) { out[i] = grp_bcast_row<CoopLayout<R>::lane_of(i)>(v); });
+    coop_for<R::N>([&](auto i) { out[i] = grp_bcast_fix<CoopLayout<R>::lane_of(i)>(out[i], v); });
 }
+
+// sum_{i<N} term_i in index order (0.0 + t0 + t1 + ...); term_i lives in lane lane_of(i).  Every term is broadcast to the
+// whole group (two 64-bit movs), so the running sum is the same in the eight lanes throughout: no hop when the walk changes
+// quads, none at the end.
 template <class R>
-__device__ __forceinline__ double coop_sum(double term) { return coop_sum_from<R, 0>(0.0, term); }
+__device__ __forceinline__ double coop_sum(double term)
+{
+    double t[R::N];
+    coop_gather<R>(term, t);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < R::N; ++i) s += t[i];
+    return s;
+}
 
 // RhsCr3bp::ode_coop (declared and explained in rk_core.h next to the reference form)
 __device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const double *p)
@@ -145,7 +154,7 @@ __device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const do
     const double d = fma(Z, Z, fma(Y, Y, w * w));
     const double r = sqrt(d);
     const double g = (hi ? mu : 1.0 - mu) / (d * r);
-    const double g1 = lo_to_hi(g, g);
+    const double g1 = lo_to_hi_only(g);         // read in the upper quad only (the lower quad's result is replaced at the end)
     const double q2 = i == 0u ? w : pos;
     const double q1 = i == 0u ? X + mu : pos;
     double lin = fma(i == 0u ? 2.0 : -2.0, sw, pos);
@@ -156,7 +165,7 @@ __device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const do
     const double r3 = r * r * r;
     const double q = i == 0u ? w : pos;
     const double T = (hi ? mu : 1.0 - mu) * q / r3;
-    const double T1 = lo_to_hi(T, T);           // upper quad: the first primary's term from the lane four below
+    const double T1 = lo_to_hi_only(T);         // upper quad: the first primary's term from the lane four below (the lower quad's result is replaced at the end)
     double lin = pos + (i == 0u ? 2.0 : -2.0) * sw;
     lin = i == 2u ? -0.0 : lin;
     const double acc = (lin - T1) - T;
@@ -228,8 +237,10 @@ struct NormOps<CoopRhs<R>, void> {
     {
         const bool hi = (threadIdx.x & 4u) != 0;
         const double r = ivp_pow(hi ? x2 : x1, hi ? e2 : e1, kz);
-        r1 = lo_to_hi(r, r);
-        r2 = hi_to_lo(r, r);
+        r1 = grp_bcast_row<0>(r);
+        r2 = grp_bcast_row<4>(r);
+        r1 = grp_bcast_fix<0>(r1, r);
+        r2 = grp_bcast_fix<4>(r2, r);
     }
 };
 

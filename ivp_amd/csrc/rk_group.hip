@@ -1,7 +1,9 @@
 // rk_group.hip -- the kernels in which several lanes share one trajectory, and their launch tables:
 //   * rk_group.h: wave-per-trajectory RK23 / DOPRI5 / DOP853 / RK4 for large state dimensions (8 < n <= 512);
-//   * rk_coop.h:  eight lanes per trajectory (n <= 8) for the latency-bound tail of a batch.  Compiled twice like rk_kernels.hip: strict (-ffp-contract=off, index-order error-norm sum) and
-// fast (-ffp-contract=fast, __shfl_xor butterfly).  Coefficients are pinned in vector registers (IVP_HOIST = 2, see
+//   * rk_coop.h:  eight lanes per trajectory (n <= 8) for the latency-bound tail of a batch.
+// Compiled twice like rk_kernels.hip, both times with -ffp-contract=off: strict (IVP_FAST = 0, index-order error-norm sum)
+// and the FMA arithmetic mode (IVP_FAST = 1: the multiply-add sites of rk_core.h spelled out as fused operations,
+// __shfl_xor butterfly in the wave-per-trajectory norms).  Coefficients are pinned in vector registers (IVP_HOIST = 2, see
 // KC() in rk_core.h): a lone wave per SIMD pays an issue slot for every re-materialised constant and has VGPRs to spare.
 #include <hip/hip_runtime.h>
 
