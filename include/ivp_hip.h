@@ -204,7 +204,9 @@ typedef struct {
 
 /* Per-trajectory results: `struct Solution` (src/solve/solution.rs:7-20) + IntegrationResult.h
  * (src/methods/mod.rs:30-39), struct-of-arrays over the batch. Any pointer may be NULL = not wanted.
- * For ivp_batch_solve() these are host pointers, for ivp_batch_solve_device() device pointers. */
+ * For ivp_batch_solve() these are host pointers, for ivp_batch_solve_device() device pointers.
+ * A capacity-bounded array (samples, log records, segments, event hits) is written up to its count; the
+ * slots past it keep what the caller put there, with host pointers as with device pointers. */
 typedef struct {
     double *y_end;      /* [n][B]  state at t_end (Solution.y.last())                           */
     double *t_end;      /* [B]     final x (xend on Success)                                    */
@@ -226,7 +228,7 @@ typedef struct {
     double *seg_cont;   /* [max_log][ncoef*n][B]  ncoef = Method::coeffs_per_state (options.rs:34-43) */
     double *seg_xold;   /* [max_log][B]                                                         */
     double *seg_h;      /* [max_log][B]                                                         */
-    uint32_t *n_seg;    /* [B]                                                                  */
+    uint32_t *n_seg;    /* [B]  segments the reference would hold (may exceed max_log); 0 for a solve without dense_output, t_eval solves included */
     /* events: Solution.t_events / Solution.y_events (src/solve/solution.rs:10-11), capped at max_events */
     double *t_events;   /* [n_events][max_events][B]                                            */
     double *y_events;   /* [n_events][max_events][n][B]                                         */
@@ -358,7 +360,9 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  *             (passes = 2), so a log is never truncated
  *   defer     in: 1 = integrate and count only (total, offsets and `out` are final on return); the records stay in the
  *             context's pool until its next solve and are fetched with ivp_step_log_fetch_device() into buffers the
- *             caller sizes from `total`
+ *             caller sizes from `total`.  "Its next solve" is ANY ivp_batch_submit_device / ivp_batch_solve* on the context,
+ *             logged or not: every submit ends the life of the deferred log, and a fetch after it returns
+ *             IVP_ERR_BAD_ARGUMENT ("no complete step log in this context's pool") without touching log->t / log->y
  * Returns IVP_ERR_LOG_CAPACITY (with total and offsets set) when the caller's t / y are too small; the records are then
  * still in the pool: enlarge the buffers and call ivp_step_log_fetch_device().
  */
@@ -384,7 +388,9 @@ int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, siz
                                   size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out,
                                   ivp_step_log_t *log, void *hip_stream);
 /* the records of the context's last logged solve (defer = 1, or after IVP_ERR_LOG_CAPACITY) into log->t / log->y
- * (device memory, `capacity` records; both NULL: allocated here); log->offsets is not touched */
+ * (device memory, `capacity` records; both NULL: allocated here); log->offsets is not touched.  That solve must be the
+ * context's LAST solve of any kind, else IVP_ERR_BAD_ARGUMENT; the same code with "the page pool ran dry ..." in
+ * ivp_last_error_string() when its pool overflowed (the records are not all there: solve again) */
 int ivp_step_log_fetch_device(ivp_ctx_t *ctx, ivp_step_log_t *log, void *hip_stream);
 /* host pointers throughout (arguments as ivp_batch_solve; log->offsets / t / y are host memory) */
 int ivp_batch_solve_logged(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0,

@@ -1055,8 +1055,13 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
         bufs = (torch.empty(max(total, 1), dtype=torch.float64, device=dev), torch.empty((max(total, 1), n), dtype=torch.float64, device=dev))
         sl.t, sl.y, sl.capacity, sl.defer = C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), max(total, 1), 0
         rc = ctx.lib.ivp_step_log_fetch_device(ctx.handle, C.byref(sl), stream)
-        if rc != 0:   # the pool had run dry: integrate again -- its size now follows the counted total
-            sl.reserve = 0   # automatic: what the first attempt asked of its fullest sub-pool
+        if rc != 0:
+            # only a pool that ran dry is answered by a second integration: the library says so (IVP_ERR_BAD_ARGUMENT, "the page
+            # pool ran dry ..."); any other failure of the fetch is the caller's to see
+            err = ctx.last_error()
+            if rc != -100 or "pool ran dry" not in err:
+                raise ConfigError(rc, err)
+            sl.reserve = 0   # automatic: the pool's size now follows the counted total (what the first attempt asked of its fullest sub-pool)
             res = solve_ivp_batch(f, t0d, t1d, y0d, pd, opts1, ctx, o1, _steplog=sl)
             sl.passes += 1
     res.log_offsets = offsets

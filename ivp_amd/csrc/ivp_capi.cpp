@@ -168,7 +168,8 @@ struct Tune {
 };
 const Tune &tune() { static const Tune t; return t; }
 // lanes (8 per trajectory) up to which the lane-cooperative kernels take over: two cooperative waves per SIMD
-// IVP_TRACE_LAUNCHES=1 with Options.profile: one stderr line per stepping-kernel launch (kind, ran / declined, duration)
+// IVP_TRACE_LAUNCHES=1 with Options.profile: one stderr line per stepping-kernel launch (kind, ran / declined, duration),
+// one when the deferred t_eval sample kernel (flavour 3) is enqueued, one per gather of the one-pass step log (ivp_log.cpp)
 bool trace_launches() { static const bool on = getenv("IVP_TRACE_LAUNCHES") != nullptr; return on; }
 size_t coop_cap_lanes(const ivp_ctx *ctx) { return tune().coop_cap_lanes ? tune().coop_cap_lanes : 2u * (size_t)ctx->one_wave_per_simd(); }
 
@@ -417,6 +418,7 @@ int finish_round(ivp_ctx *ctx, int *done)
         // deferred t_eval sampling: every trajectory has finished stepping; its noted steps are evaluated now, one lane each
         // (the solve is complete when THIS kernel is: one more turn of the round-done event)
         P.sampled = true;
+        if (trace_launches() && P.profile) fprintf(stderr, "ivp launch sample  deferred t_eval sampling, %zu trajectories\n", P.B);
         const bool fast = P.fp_mode == IVP_FP_FAST;
         LAUNCH_TRY(ctx, (fast ? ivp_launch_fast : ivp_launch_strict)(IVP_LAUNCH_SAMPLE, P.method, P.prob.rhs_id, 3, P.a, (uint32_t)P.B, P.stream));
         HIP_TRY(ctx, hipEventRecord(P.round_done, P.stream));
@@ -510,6 +512,7 @@ int ivp_ctx_create(ivp_ctx_t **out, int device)
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
         c->cus = (uint32_t)prop.multiProcessorCount;
         c->simds = c->cus * 4u;   // CDNA: four SIMDs per compute unit
+        if (prop.sharedMemPerBlock > 0) c->lds_per_block = prop.sharedMemPerBlock;
     }
     if (hipHostMalloc((void **)&c->pinned, 64 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
         delete c;
@@ -611,7 +614,10 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
     const bool paged = ctx->log_plan.want;
     const uint64_t log_reserve = ctx->log_plan.reserve;
     ctx->log_plan = ivp_ctx::LogPlan{};
-    if (paged) { ctx->log_state.valid = false; ctx->log_state.overflow = false; }
+    // EVERY solve ends the life of the log in the pool: a non-paged full solve rewrites (or, through DevBuf::reserve, frees) the
+    // counts log_state.n_log points at, so a fetch that comes after it must fail (BAD_ARGUMENT), not gather from stale counts
+    ctx->log_state.valid = false;
+    ctx->log_state.overflow = false;
     if (paged && opt->t_eval) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "the accepted-step log is what solve_ivp records when t_eval is None");
 
     const bool want_eval = opt->t_eval != nullptr;
@@ -733,8 +739,29 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
     // built-in thread-per-trajectory problems.  The stepping kernels note the sampled steps, a second kernel with one lane per
     // noted step evaluates the dense stages and the samples (rk_core.h so_defer_samples / dop853_sample_body): in lock-step a
     // wave pays DOP853's three dense stages whenever ANY of its trajectories has a sample in the step.
-    const bool defer_eval = want_eval && opt->method == IVP_DOP853 && !want_dense && n_events == 0 && !group && prob->rhs_id != IVP_RHS_JIT &&
-                            opt->n_eval > 0 && tune().defer_eval != 0;
+    // The noted steps take 8 (n + 4) max_grid B bytes (def_rec); a block that does not fit -- the rule of evd_rec below, and
+    // IVP_DEFER_EVAL_BYTES as an upper bound, read per call -- leaves the sampling in the stepping kernels (flavour 1), which
+    // delivers the same bits.  Decided HERE, before anything is derived from defer_eval (the n_seg binding, P.full).
+    bool defer_eval = want_eval && opt->method == IVP_DOP853 && !want_dense && n_events == 0 && !group && prob->rhs_id != IVP_RHS_JIT &&
+                      opt->n_eval > 0 && tune().defer_eval != 0;
+    uint64_t def_cap = 0;
+    if (defer_eval) {   // noted steps: at most one per t_eval point of a trajectory (every noted step holds a sample)
+        def_cap = (uint64_t)opt->n_eval;
+        if (opt->t_eval_offsets) {
+            def_cap = 0;
+            for (size_t b = 0; b < B; ++b) def_cap = std::max<uint64_t>(def_cap, opt->t_eval_offsets[b + 1] - opt->t_eval_offsets[b]);
+        }
+        def_cap = std::max<uint64_t>(def_cap, 1);
+        const uint64_t bytes = sizeof(double) * def_cap * (uint64_t)(n + 4) * B;
+        size_t free_b = 0, total_b = 0;
+        bool fits = def_cap <= 0xFFFFFFFFull && (bytes <= ctx->def_rec.cap || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= (free_b + ctx->def_rec.cap) / 4));
+        if (const char *cap = std::getenv("IVP_DEFER_EVAL_BYTES")) {
+            const unsigned long long v = std::strtoull(cap, nullptr, 10);
+            if (v > 0 && bytes > v) fits = false;
+        }
+        if (fits && ctx->def_rec.reserve((size_t)bytes) != hipSuccess) { (void)hipGetLastError(); fits = false; }
+        if (!fits) defer_eval = false;
+    }
     if (n_events > 0) {   // event state: prev_event, hit counters; outputs where given
         for (int i = 0; i < 4; ++i) { a.ev_direction[i] = opt->ev_direction[i]; a.ev_terminal[i] = opt->ev_terminal[i]; }
         if (opt->ev_direction_vec && opt->ev_terminal_vec && opt->n_event_cfg == n_events) {   // any number of event functions
@@ -793,20 +820,21 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
                 a.teval_extra = n_events > 0 ? 1u : 0u;
             }
         }
-        if (defer_eval) {   // noted steps: at most one per t_eval point of a trajectory (every noted step holds a sample)
-            uint64_t cap = (uint64_t)opt->n_eval;
-            if (opt->t_eval_offsets) {
-                cap = 0;
-                for (size_t b = 0; b < B; ++b) cap = std::max<uint64_t>(cap, opt->t_eval_offsets[b + 1] - opt->t_eval_offsets[b]);
-            }
-            cap = std::max<uint64_t>(cap, 1);
-            HIP_TRY(ctx, ctx->def_rec.reserve(sizeof(double) * (size_t)cap * (size_t)(n + 4) * B));
+        if (defer_eval) {   // (reserved above)
             a.def_rec = (double *)ctx->def_rec.p;
-            a.def_cap = (uint32_t)cap;
+            a.def_cap = (uint32_t)def_cap;
         }
         BIND(n_filled, out->n_filled, sc_n_filled, sizeof(int32_t) * B);
         BIND(n_log, out->n_log, sc_n_log, sizeof(uint32_t) * B);
-        BIND(n_seg, out->n_seg, sc_n_seg, sizeof(uint32_t) * B);
+        if (defer_eval) {
+            // flavour 3 counts a trajectory's noted steps in n_seg: that is the context's scratch, never the caller's array, which
+            // gets what flavour 1 and the reference give for a solve without dense output -- no segments
+            HIP_TRY(ctx, ctx->sc_n_seg.reserve(sizeof(uint32_t) * B));
+            a.n_seg = (uint32_t *)ctx->sc_n_seg.p;
+            if (out->n_seg) HIP_TRY(ctx, hipMemsetAsync(out->n_seg, 0, sizeof(uint32_t) * B, s));
+        } else {
+            BIND(n_seg, out->n_seg, sc_n_seg, sizeof(uint32_t) * B);
+        }
         HIP_TRY(ctx, ctx->sc_next_idx.reserve(sizeof(int32_t) * B));
         HIP_TRY(ctx, ctx->sc_t_last.reserve(sizeof(double) * B));
         a.next_idx = (int32_t *)ctx->sc_next_idx.p;
@@ -1291,6 +1319,17 @@ int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_
             if (member(out, md[k]) && bytes) {
                 HIP_TRY(c0, ctx->st_out[k].reserve(bytes));
                 member(&S.out, md[k]) = ctx->st_out[k].p;
+                // The kernels write only the slots they fill (event hits, samples, log records, segments up to their counts), and
+                // the whole mirror returns to the host: it starts from the caller's content, as a caller's device array does, not
+                // from what an earlier solve left in the staging buffer.  A CSR step log is sized to its counts and filled whole.
+                if (is_log_member(md[k])) continue;
+                const void *host = member(out, md[k]);
+                if (is_eval_member(md[k])) {
+                    const EvalRun run = eval_run(opt, S.first, m, grid_events);
+                    const size_t rec = eval_rec_bytes(md[k]);
+                    if (run.count) HIP_TRY(c0, hipMemcpyAsync(ctx->st_out[k].p, (const char *)host + run.first * rec, run.count * rec, hipMemcpyHostToDevice, nullptr));
+                } else
+                    HIP_TRY(c0, copy_rows(ctx->st_out[k].p, m, (const char *)host + S.first * md[k].elem, B, md[k].elem, m, md[k].rows, hipMemcpyHostToDevice, nullptr));
             }
         }
     }

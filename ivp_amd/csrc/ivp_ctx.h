@@ -46,6 +46,7 @@ struct ivp_ctx {
     // 4 SIMDs and wave64; multiProcessorCount is 256 on MI355X, 304 on MI300X, fewer on a partitioned device.
     uint32_t cus = 256, simds = 1024;
     uint32_t one_wave_per_simd() const { return simds * (uint32_t)IVP_WAVE; }   // lanes that fill every SIMD with one wave
+    size_t lds_per_block = 65536;   // LDS a workgroup may use (sharedMemPerBlock): 160 KB on gfx950, 64 KB on gfx942; sizes the log gather's workgroups
     std::string err;
     // scratch (device)
     ivp_host::DevBuf k1, facold, hlamb, flags, perm[2], counts, slot, ran, teval, teval_off, evcfg, tolvec, zero_off;

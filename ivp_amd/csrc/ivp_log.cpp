@@ -104,8 +104,10 @@ int device_destination(ivp_ctx *ctx, ivp_step_log_t *log, uint64_t total, int n,
 int gather_pool(ivp_ctx *ctx, const unsigned long long *offsets_dev, uint64_t capacity, uint64_t dst_base, double *t, double *y, hipStream_t s)
 {
     const ivp_ctx::LogState &LS = ctx->log_state;
+    static const bool trace = std::getenv("IVP_TRACE_LAUNCHES") != nullptr;
+    if (trace && ctx->pend.profile) fprintf(stderr, "ivp launch gather  n = %d, %u wave(s) per workgroup, LDS limit %zu B\n", LS.n, ivp_log_gather_waves(LS.n, ctx->lds_per_block), ctx->lds_per_block);
     HIP_TRY(ctx, ivp_log_gather((const double *)ctx->log_pool.p, LS.region, (const unsigned long long *)ctx->log_alloc.p, LS.subs, LS.max_arenas, offsets_dev, LS.B, LS.n,
-                                capacity, dst_base, t, y, s));
+                                capacity, dst_base, t, y, ctx->lds_per_block, s));
     return IVP_OK;
 }
 
@@ -240,6 +242,8 @@ int ivp_batch_solve_logged(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
         if (!member(out, md[k]) || !bytes || is_log(md[k])) continue;
         HIP_TRY(ctx, ctx->st_out[k].reserve(bytes));
         member(&dev, md[k]) = ctx->st_out[k].p;
+        // slots the kernels do not fill (event hits past their count) return as the caller gave them, not as an earlier solve left them
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->st_out[k].p, member(out, md[k]), bytes, hipMemcpyHostToDevice, nullptr));
     }
     HIP_TRY(ctx, ctx->st_logoff.reserve(sizeof(unsigned long long) * (B + 1)));
     // ---- integrate once; the records stay in the pool until their number is known ----

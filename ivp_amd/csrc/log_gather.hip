@@ -217,21 +217,39 @@ hipError_t ivp_log_scan(const uint32_t *n_log, size_t B, unsigned long long *off
     return hipGetLastError();
 }
 
+// static LDS of log_gather_kernel (s_slots) next to its dynamic tiles
+constexpr size_t kGatherStaticLds = (size_t)kGatherWaves * 8u * IVP_LOG_SLOTS;
+
+uint32_t ivp_log_gather_waves(int n, size_t lds_limit)
+{
+    const uint32_t np1 = (uint32_t)n + 1u;
+    if (np1 > 9u) return 0;
+    const size_t group = (size_t)IVP_LOG_SLOTS * IVP_LOG_GROUP(np1) * np1 * sizeof(double);   // 32 slots x 8 columns x (n + 1) doubles
+    for (uint32_t w = kGatherWaves; w >= 1u; w >>= 1)
+        if (group * w + kGatherStaticLds <= lds_limit) return w;
+    return 0;
+}
+
 hipError_t ivp_log_gather(const double *pool, unsigned long long region, const unsigned long long *alloc, uint32_t subs, uint32_t max_arenas,
                           const unsigned long long *offsets, size_t B, int n, unsigned long long capacity, unsigned long long dst_base,
-                          double *t_log, double *y_log, hipStream_t s)
+                          double *t_log, double *y_log, size_t lds_limit, hipStream_t s)
 {
     if (B == 0 || max_arenas == 0) return hipSuccess;
     (void)hipGetLastError();
-    // n <= 8: four wavefronts per workgroup, each with LDS for a whole column group (32 slots x 8 columns x (n + 1) doubles);
-    // larger systems (one column per group, the group walked in tiles of at most 32 KB of its slots): one wavefront
+    // n <= 8: up to four wavefronts per workgroup, each with LDS for a whole column group (32 slots x 8 columns x (n + 1)
+    // doubles: 72 KB + 1 KB static for four waves at n = 8) -- as many of 4, 2, 1 as the device's per-workgroup LDS holds;
+    // larger systems (one column per group), and small ones where not even one whole group fits: one wavefront that walks
+    // the group in tiles of at most 32 KB of its slots
     const uint32_t np1 = (uint32_t)n + 1u, row = IVP_LOG_GROUP(np1) * np1;
-    const bool small = np1 <= 9u;
-    const uint32_t tile_doubles = small ? IVP_LOG_SLOTS * row : std::max<uint32_t>(row, std::min<uint32_t>(IVP_LOG_SLOTS * row, 4096u));
-    const dim3 grid(max_arenas, subs), block(small ? kGatherThreads : IVP_WAVE);
-    const size_t lds = (size_t)tile_doubles * sizeof(double) * (small ? kGatherWaves : 1);
+    const uint32_t waves = ivp_log_gather_waves(n, lds_limit);
+    const bool small = waves != 0u;
+    const size_t room = lds_limit > kGatherStaticLds ? (lds_limit - kGatherStaticLds) / sizeof(double) : 0;
+    const uint32_t tile_doubles = small ? IVP_LOG_SLOTS * row
+                                        : std::max<uint32_t>(row, (uint32_t)std::min<size_t>(std::min<size_t>(IVP_LOG_SLOTS * row, 4096u), room));
+    const dim3 grid(max_arenas, subs), block(small ? waves * IVP_WAVE : IVP_WAVE);
+    const size_t lds = (size_t)tile_doubles * sizeof(double) * (small ? waves : 1);
 #define IVP_GATHER_CASE(NP1) case NP1: hipLaunchKernelGGL((log_gather_kernel<NP1>), grid, block, lds, s, pool, region, alloc, offsets, (uint32_t)B, (uint32_t)n, capacity, dst_base, t_log, y_log, tile_doubles); break;
-    switch (n + 1) {
+    switch (small ? n + 1 : 0) {
         IVP_GATHER_CASE(2) IVP_GATHER_CASE(3) IVP_GATHER_CASE(4) IVP_GATHER_CASE(5) IVP_GATHER_CASE(6) IVP_GATHER_CASE(7) IVP_GATHER_CASE(8) IVP_GATHER_CASE(9)
     default: hipLaunchKernelGGL((log_gather_kernel<0>), grid, block, lds, s, pool, region, alloc, offsets, (uint32_t)B, (uint32_t)n, capacity, dst_base, t_log, y_log, tile_doubles); break;
     }

@@ -198,6 +198,10 @@ def solve_batch(rhs, y0, params, t0, t1, *, method="DOPRI5", rtol=1e-3, atol=1e-
         cap = max(len(np.atleast_1d(t_eval)), 1)
         res["def_rec"] = np.full((cap, n + 4, B), np.nan)
         a.def_rec, a.def_cap = p(res["def_rec"]), cap
+        # the library's binding (ivp_capi.cpp): flavour 3 counts the noted steps in n_seg, which is scratch -- the caller's n_seg
+        # stays what a solve without dense output gives, zero
+        res["def_cnt"] = np.zeros(B, dtype=np.uint32)
+        a.n_seg = p(res["def_cnt"])
     rc = L.emul_solve(m, rid, flavour, C.byref(a), C.byref(chunks))
     if rc == -5:
         raise ValueError("IVP_ERR_INVALID_STEP_SIZE")

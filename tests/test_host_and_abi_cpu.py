@@ -342,3 +342,60 @@ def test_bench_step_loop_strong_scaling_under_gloo_world_size_2(tmp_path):
     outs = [p.communicate(timeout=300)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o
+
+
+class _StubLoggedLib:
+    """stands in for libivp_hip.so behind solve_ivp_batch_logged: the logged solve "succeeds" (5 records), the fetch fails with
+    the given code and the context reports the given message"""
+
+    def __init__(self, real, fetch_rc):
+        self._real, self.fetch_rc, self.solves, self.fetches = real, fetch_rc, 0, 0
+
+    def __getattr__(self, name):
+        return getattr(self._real, name)
+
+    def ivp_batch_solve_logged_device(self, *args):
+        self.solves += 1
+        sl = args[-2]._obj
+        sl.total, sl.passes = 5, 1
+        return 0
+
+    def ivp_step_log_fetch_device(self, *args):
+        self.fetches += 1
+        return self.fetch_rc
+
+
+class _StubCtx:
+    device, handle = 0, None
+
+    def __init__(self, lib, message):
+        self.lib, self.message, self._scalars = lib, message, {}
+
+    def last_error(self):
+        return self.message
+
+
+def test_logged_solve_integrates_again_only_when_the_pool_ran_dry(lib, monkeypatch):
+    """solve_ivp_batch_logged used to answer ANY failure of ivp_step_log_fetch_device with a second integration and call it
+    "the pool ran dry".  Only the library's own report of a dry pool (IVP_ERR_BAD_ARGUMENT, "the page pool ran dry ...") is
+    answered that way; everything else is raised.  CPU tensors, a stub library: no GPU involved."""
+    import types
+    import torch
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: types.SimpleNamespace(cuda_stream=0))
+    y0 = torch.zeros((2, 3), dtype=torch.float64)
+    stub = _StubLoggedLib(lib, -103)
+    with pytest.raises(ivp_amd.ConfigError) as e:
+        ivp_amd.solve_ivp_batch_logged(ivp_amd.SHO(), 0.0, 1.0, y0, None, ivp_amd.Options(), _StubCtx(stub, "hipMalloc: out of memory"))
+    assert e.value.code == -103 and "out of memory" in str(e.value) and (stub.solves, stub.fetches) == (1, 1)
+    # IVP_ERR_BAD_ARGUMENT for another reason (no log in the pool) is not a dry pool either
+    stub = _StubLoggedLib(lib, -100)
+    with pytest.raises(ivp_amd.ConfigError):
+        ivp_amd.solve_ivp_batch_logged(ivp_amd.SHO(), 0.0, 1.0, y0, None, ivp_amd.Options(), _StubCtx(stub, "no complete step log in this context's pool"))
+    assert (stub.solves, stub.fetches) == (1, 1)
+    # the dry pool: the message ivp_step_log_fetch_device gives after an overflow
+    stub = _StubLoggedLib(lib, -100)
+    msg = "the page pool ran dry during the last logged solve: solve again (the pool is sized from the counted total now)"
+    r = ivp_amd.solve_ivp_batch_logged(ivp_amd.SHO(), 0.0, 1.0, y0, None, ivp_amd.Options(), _StubCtx(stub, msg))
+    assert (stub.solves, stub.fetches) == (2, 1) and r.log_info["passes"] == 2 and r.log_info["records"] == 5
+    src = open(os.path.join(ROOT, "ivp_amd", "csrc", "ivp_log.cpp")).read()
+    assert '"the page pool ran dry' in src     # the words api.py looks for are the library's

@@ -122,6 +122,9 @@ def test_deferred_t_eval_sampling_equals_sampling_in_the_stepping_bodies(rhs, ma
     for k in ("y_eval", "y_end", "t_end", "h_next"):
         assert np.array_equal(_bits(deferred[k]), _bits(inline[k])), k
     assert int(deferred["n_filled"].min()) > 10
+    # the noted-step counter of flavour 3 is scratch: n_seg of a solve without dense output is zero in both flavours
+    assert not deferred["n_seg"].any() and not inline["n_seg"].any()
+    assert np.array_equal(deferred["def_cnt"].astype(np.int64) > 0, deferred["n_filled"] > 0)
     # backward in time, a grid running backward
     back = dict(method="DOP853", rtol=rtol, atol=1e-11, t_eval=np.linspace(t1s, 0.0, 23)[1:], chunk=chunk)
     a = emul_batch(rhs, y0, p, t1s, 0.0, defer_eval=False, **back)
