@@ -470,6 +470,63 @@ int ivp_dense_eval_device(ivp_ctx_t *ctx, int32_t method, int32_t n, int32_t fp_
                           void *hip_stream);
 
 /*
+ * Every trajectory's complete Solution.t_events / Solution.y_events (src/solve/solution.rs:10-11: Vecs that grow with
+ * every occurrence, src/solve/solout.rs:158-331) in CSR form: the events of B solve_ivp() calls without the max_events cap.
+ *
+ *     the k-th occurrence of event i on trajectory b is record q = offsets[i * B + b] + k:  t[q],  y[q * n + c]
+ * Runs are event-major (run r = i * B + b: all roots of event i over the batch are ONE contiguous slice,
+ * offsets[i * B] .. offsets[(i + 1) * B)), records within a run in detection order; offsets[n_events * B] = total.
+ * n_events * B may not exceed 4294967295; a problem without event functions is IVP_ERR_BAD_ARGUMENT.
+ *
+ * How: a counting solve (the solve itself: `out` receives every member as in ivp_batch_solve_device -- end state, t_eval
+ * samples, bounded step log and dense segments -- and n_event_hits, if given, the counts) with a temporary block of
+ * opt->max_events slots per event and trajectory (max_events = 0: count only), an exclusive scan of the counts into
+ * `offsets`, then the records: from the counting solve's own block when every run fits opt->max_events (passes = 1, ONE
+ * integration), else from a filling solve over trajectory ranges (t_eval, step log, dense output and profiling off) whose
+ * bounded blocks, [n_events][max hits of the range][n + 1] doubles per trajectory, fit half of the free device memory,
+ * packed into the CSR arrays (passes = 2).  out->t_events / y_events must be NULL: they are the bounded layout.
+ * PEAK device memory: the result plus that staging block (reported in staging_bytes) plus the scratch of the solve that
+ * fills it -- for explicit methods without a terminal event the deferred event refinement notes up to n_events * max_events
+ * steps of 4 + 3 n_events + n + ncoef n doubles per trajectory (about six staging blocks for n = 6, DOPRI5) when a quarter
+ * of the free memory holds them, and refines inline otherwise.  The environment variable IVP_EVENT_STAGING_BYTES caps
+ * the staging block (and with it that scratch), at the price of one filling solve per range.
+ *
+ * ivp_event_log_t -- who owns what (as ivp_dense_log_t):
+ *   offsets   [n_events * B + 1], ALWAYS the caller's (device memory for the device form, host memory for the host form)
+ *   t, y      the caller's buffers of `capacity` records ([capacity], [capacity][n]), or both NULL: the library allocates
+ *             exactly `total` records (hipMalloc on the context's device, malloc for the host form), sets owned = 1, and
+ *             the caller releases them with ivp_event_log_free()
+ * Returns IVP_ERR_LOG_CAPACITY (with total and offsets set) when the caller's buffers are too small, IVP_ERR_HIP with a
+ * message when the device has not the memory for the result or the staging: never a truncated log.
+ */
+typedef struct {
+    uint64_t *offsets;
+    double *t;
+    double *y;
+    uint64_t capacity;
+    /* ---- out ---- */
+    int32_t owned;            /* 1: t / y were allocated by the library                                            */
+    int32_t device;           /* HIP device of owned device memory, -1 for host memory                             */
+    uint32_t passes;          /* integrations it took: 1 (every run fitted the counting solve's block) or 2         */
+    uint32_t n_events;        /* event functions of the problem: offsets holds n_events * B + 1 entries            */
+    uint64_t total;           /* number of records = offsets[n_events * B]                                         */
+    uint64_t staging_bytes;   /* largest bounded event block a solve of this call wrote into                       */
+} ivp_event_log_t;
+
+int ivp_batch_solve_events_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0,
+                                  const double *params, const double *t0, size_t t0_len, const double *t1,
+                                  size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out,
+                                  ivp_event_log_t *ev, void *hip_stream);
+/* host pointers throughout (arguments as ivp_batch_solve; ev->offsets / t / y are host memory) */
+int ivp_batch_solve_events(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           ivp_batch_result_t *out, ivp_event_log_t *ev);
+/* an owned device log (owned = 1, device >= 0) into the caller's device buffers of ev->total records, on hip_stream;
+ * the owned memory is released and ev then points at the caller's buffers (owned = 0) */
+int ivp_event_log_fetch_device(ivp_event_log_t *ev, double *t, double *y, void *hip_stream);
+void ivp_event_log_free(ivp_event_log_t *ev);
+
+/*
  * One batch over several devices.  The reference has no parallelism (a batch is B back-to-back solve_ivp() calls,
  * src/solve/solve_ivp.rs:99-313, with no coupling between them), so the batch shards by trajectory range: shard k is
  * integrated by its own context on its own device with no communication, and the only data movement is the final

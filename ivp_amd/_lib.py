@@ -65,6 +65,13 @@ class DenseLogT(C.Structure):
                 ("staging_bytes", C.c_uint64)]
 
 
+class EventLogT(C.Structure):
+    """ivp_event_log_t: every trajectory's t_events / y_events as a CSR log, runs event-major (ivp_batch_solve_events*())."""
+    _fields_ = [("offsets", C.c_void_p), ("t", C.c_void_p), ("y", C.c_void_p), ("capacity", C.c_uint64),
+                ("owned", C.c_int32), ("device", C.c_int32), ("passes", C.c_uint32), ("n_events", C.c_uint32), ("total", C.c_uint64),
+                ("staging_bytes", C.c_uint64)]
+
+
 class ShardT(C.Structure):
     """ivp_shard_t: trajectories [first, first + count) of a batch, resident on ctx's device (SoA stride count)."""
     _fields_ = [("ctx", C.c_void_p), ("first", C.c_size_t), ("count", C.c_size_t),
@@ -90,6 +97,7 @@ EXPORTS = (
     "ivp_rhs_compile", "ivp_rhs_compile_events", "ivp_rhs_compile_ex", "ivp_rhs_free",
     "ivp_batch_solve_logged", "ivp_batch_solve_logged_device", "ivp_step_log_fetch_device", "ivp_step_log_free", "ivp_batch_solve_logged_multi", "ivp_step_log_fetch_multi",
     "ivp_batch_solve_dense_device", "ivp_batch_solve_dense", "ivp_dense_log_fetch_device", "ivp_dense_log_free", "ivp_dense_eval_device",
+    "ivp_batch_solve_events_device", "ivp_batch_solve_events", "ivp_event_log_fetch_device", "ivp_event_log_free",
 )
 
 ERRORS = {
@@ -185,6 +193,14 @@ def load():
     L.ivp_dense_eval_device.restype = C.c_int
     L.ivp_dense_eval_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ivp_batch_solve_events_device.restype = C.c_int
+    L.ivp_batch_solve_events_device.argtypes = solve_args + [C.POINTER(EventLogT), C.c_void_p]
+    L.ivp_batch_solve_events.restype = C.c_int
+    L.ivp_batch_solve_events.argtypes = solve_args + [C.POINTER(EventLogT)]
+    L.ivp_event_log_fetch_device.restype = C.c_int
+    L.ivp_event_log_fetch_device.argtypes = [C.POINTER(EventLogT), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ivp_event_log_free.restype = None
+    L.ivp_event_log_free.argtypes = [C.POINTER(EventLogT)]
     L.ivp_rhs_compile.restype = C.c_int
     L.ivp_rhs_compile.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.ivp_rhs_compile_events.restype = C.c_int

@@ -689,6 +689,12 @@ class BatchSolution:
     seg_offsets: object = None
     dense: object = None          # solve_ivp_batch_dense: BatchContinuousOutput over those segments (Solution.sol of every trajectory)
     dense_info: dict = field(default_factory=dict)   # solve_ivp_batch_dense: passes, segments, bytes, staging_bytes
+    # CSR event log (solve_ivp_batch_events): [n_events*B+1] record offsets, run i * B + b = event i on trajectory b;
+    # t_events_csr [total], y_events_csr [total, n]
+    event_offsets: object = None
+    t_events_csr: object = None
+    y_events_csr: object = None
+    event_info: dict = field(default_factory=dict)   # solve_ivp_batch_events: passes, total, staging_bytes
 
     def eval_of(self, b: int):
         """(index into trajectory b's own t_eval grid, y) of its emitted samples (per-trajectory grids); index -1 marks the
@@ -701,6 +707,25 @@ class BatchSolution:
         """(t, y) of trajectory b from a CSR step log: Solution.t / Solution.y of that solve_ivp() call."""
         lo, hi = int(self.log_offsets[b]), int(self.log_offsets[b + 1])
         return self.t_log[lo:hi], self.y_log[lo:hi]
+
+    def events_of(self, b: int, i: int):
+        """(t, y) of every occurrence of event i on trajectory b from a CSR event log, in detection order:
+        Solution.t_events[i] / Solution.y_events[i] of that solve_ivp() call."""
+        B = int(self.t_end.shape[0])
+        lo, hi = int(self.event_offsets[i * B + b]), int(self.event_offsets[i * B + b + 1])
+        return self.t_events_csr[lo:hi], self.y_events_csr[lo:hi]
+
+    def events_all(self, i: int):
+        """(t, y, trajectory) of every occurrence of event i over the whole batch -- one contiguous slice of the CSR
+        event log (the runs are event-major), ordered by trajectory; the trajectory index of every record is computed
+        on the device from the offsets."""
+        import torch
+        B = int(self.t_end.shape[0])
+        run = self.event_offsets[i * B:(i + 1) * B + 1]
+        lo, hi = int(run[0]), int(run[-1])
+        q = torch.arange(lo, hi, dtype=run.dtype, device=run.device)
+        traj = torch.bucketize(q, run[1:], right=True)   # the run that holds record q: the first whose end lies past q
+        return self.t_events_csr[lo:hi], self.y_events_csr[lo:hi], traj
 
 
 # ------------------------------------------------------------------------------------------------
@@ -770,7 +795,7 @@ class PendingBatch:
 
 
 def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None):
+                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None):
     """B independent ``solve_ivp(f, t0[b], t1[b], y0[:, b], options)`` calls on the GPU.
 
     ``y0``: ``[n, B]`` float64, numpy (host path: staged through the library) or a CUDA torch tensor
@@ -929,7 +954,11 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
             copt.ev_terminal_vec = terms.ctypes.data_as(C.POINTER(C.c_uint32))
             copt.n_event_cfg = ne_ev
         mev = max(int(options.max_events), 1)
-        if res.t_events is None:
+        if _events is not None:   # solve_ivp_batch_events: the occurrences go to the CSR log, the counts come back
+            if res.n_event_hits is None:
+                res.n_event_hits = xp_zeros((ne_ev, B), u32)
+                res.t_term = xp_zeros((B,), f64)
+        elif res.t_events is None:
             res.t_events = xp_zeros((ne_ev, mev, B), f64)
             res.y_events = xp_zeros((ne_ev, mev, n, B), f64)
             res.n_event_hits = xp_zeros((ne_ev, B), u32)
@@ -955,6 +984,13 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
         rc = ctx.lib.ivp_batch_solve_dense_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
                                                   ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_dense), stream)
+    elif _events is not None:   # solve_ivp_batch_events: counting solve + scan + the occurrences as a CSR log
+        import torch
+        if not on_device:
+            raise ValueError("the CSR event log takes device arrays")
+        stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
+        rc = ctx.lib.ivp_batch_solve_events_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                   ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_events), stream)
     elif _steplog is not None:   # solve_ivp_batch_logged: ONE integration that also records every accepted step (page pool + gather)
         import torch
         if not on_device:
@@ -1188,6 +1224,53 @@ def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = No
     res.seg_cont, res.seg_xold, res.seg_h = cont[:total], xold[:total], h[:total]
     res.dense_info = {"passes": int(dl.passes), "segments": total, "bytes": total * (nc + 2) * 8, "staging_bytes": int(dl.staging_bytes)}
     res.dense = BatchContinuousOutput(options.method_enum, int(y0d.shape[0]), offsets, res.seg_cont, res.seg_xold, res.seg_h, options.fp_mode, ctx)
+    return res
+
+
+def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None) -> BatchSolution:
+    """B independent ``solve_ivp`` calls with EVERY occurrence of every event (``Solution.t_events`` / ``y_events``,
+    src/solve/solution.rs:10-11), not capped at ``max_events``: the occurrences come back as a CSR log on the device.
+
+    The members of the result are those of ``solve_ivp_batch`` with the same options (end state, t_eval samples, bounded
+    step log and dense segments, ``n_event_hits`` [n_events, B]) except the bounded ``t_events`` / ``y_events``, plus
+    ``event_offsets`` [n_events*B + 1], ``t_events_csr`` [total], ``y_events_csr`` [total, n] and ``event_info``: the
+    k-th occurrence of event i on trajectory b is record ``event_offsets[i*B + b] + k``.  ``events_of(b, i)`` slices one
+    run, ``events_all(i)`` all roots of event i over the batch with their trajectory indices (a Poincare section).
+    How (``ivp_batch_solve_events_device``): a counting solve with a temporary block of ``max_events`` slots, an exclusive
+    scan of the counts, then the records -- packed from the counting solve's block when every run fits ``max_events``
+    (``event_info["passes"]`` = 1: one integration), else from a filling solve over trajectory ranges whose bounded blocks
+    of [n_events][max hits][n + 1] doubles per trajectory are packed into the CSR arrays (``passes`` = 2).
+    ``max_events=0`` counts first and always fills.  The library-owned log is copied once into the returned tensors (the
+    total is not known before the solve), so the result is briefly held twice.  The log cannot overflow, so no overflow warning is ever issued;
+    ``IVP_EVENT_STAGING_BYTES`` caps the staging block at the price of one filling solve per trajectory range."""
+    import torch
+    options = options or Options()
+    if not f.n_events():
+        raise ValueError("solve_ivp_batch_events: the problem defines no event functions")
+    ctx = ctx or default_context(y0.device.index or 0 if _is_torch(y0) else 0)
+    dev = y0.device if _is_torch(y0) else torch.device("cuda", ctx.device)
+    to_dev = lambda a: None if a is None else (a if _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev))
+    y0d, pd = to_dev(y0), to_dev(params)
+    tt = lambda v: v if (np.ndim(v) == 0 and not _is_torch(v)) else to_dev(v)
+    t0d, t1d = tt(t0), tt(t1)
+    n, B = int(y0d.shape[0]), int(y0d.shape[1])
+    el = _lib.EventLogT()
+    offsets = torch.zeros(f.n_events() * B + 1, dtype=torch.int64, device=dev)
+    el.offsets = offsets.data_ptr()
+    try:
+        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, options, ctx, _events=el)
+        total = int(el.total)
+        t = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        y = torch.empty((max(total, 1), n), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = ctx.lib.ivp_event_log_fetch_device(C.byref(el), C.c_void_p(t.data_ptr()), C.c_void_p(y.data_ptr()), stream)
+        if rc != 0:
+            raise ConfigError(rc, "ivp_event_log_fetch_device")
+    finally:
+        ctx.lib.ivp_event_log_free(C.byref(el))   # owned device memory the fetch did not take over (an error on the way)
+    res.event_offsets = offsets
+    res.t_events_csr, res.y_events_csr = t[:total], y[:total]
+    res.event_info = {"passes": int(el.passes), "total": total, "staging_bytes": int(el.staging_bytes)}
     return res
 
 

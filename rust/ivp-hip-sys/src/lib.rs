@@ -175,6 +175,23 @@ pub struct ivp_dense_log_t {
     pub staging_bytes: u64,
 }
 
+/// Every trajectory's Solution.t_events / y_events as a CSR log (src/solve/solution.rs:10-11): the k-th occurrence of
+/// event i on trajectory b is record offsets[i * B + b] + k (runs event-major); t / y null on entry = allocated by the
+/// library (`owned` = 1; release with `ivp_event_log_free`).
+#[repr(C)]
+pub struct ivp_event_log_t {
+    pub offsets: *mut u64,
+    pub t: *mut f64,
+    pub y: *mut f64,
+    pub capacity: u64,
+    pub owned: i32,
+    pub device: i32,
+    pub passes: u32,
+    pub n_events: u32,
+    pub total: u64,
+    pub staging_bytes: u64,
+}
+
 pub enum ivp_ctx_t {}
 
 /// trajectories [first, first + count) of a batch, resident on ctx's device (SoA stride `count`)
@@ -242,6 +259,16 @@ extern "C" {
     pub fn ivp_dense_eval_device(ctx: *mut ivp_ctx_t, method: i32, n: i32, fp_mode: i32, b: usize, offsets: *const u64,
                                  cont: *const f64, xold: *const f64, h: *const f64, t: *const f64, t_offsets: *const u64,
                                  m: u64, extrapolate: i32, y: *mut f64, found: *mut i32, hip_stream: *mut c_void) -> c_int;
+    // Solution.t_events / y_events of every trajectory without the max_events cap: the occurrences in CSR form
+    pub fn ivp_batch_solve_events_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64,
+                                         params: *const f64, t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize,
+                                         opt: *const ivp_options_t, out: *mut ivp_batch_result_t, ev: *mut ivp_event_log_t,
+                                         hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_batch_solve_events(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                  t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                  out: *mut ivp_batch_result_t, ev: *mut ivp_event_log_t) -> c_int;
+    pub fn ivp_event_log_fetch_device(ev: *mut ivp_event_log_t, t: *mut f64, y: *mut f64, hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_event_log_free(ev: *mut ivp_event_log_t);
     // one batch over several devices: N contexts driven by this thread, shards gathered by peer copies (xGMI)
     pub fn ivp_batch_solve_multi(shards: *mut ivp_shard_t, n_shards: i32, prob: *const ivp_problem_t, b: usize,
                                  opt: *const ivp_options_t, gather_device: i32, gathered: *mut ivp_batch_result_t) -> c_int;
