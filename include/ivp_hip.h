@@ -615,6 +615,29 @@ int ivp_rhs_compile_events(ivp_ctx_t *ctx, const char *source, int32_t n, int32_
 int ivp_rhs_compile_ex(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags, void **handle);
 void ivp_rhs_free(void *handle);
 
+/*
+ * Jacobian sparsity for BDF on 8 < n <= 512 (the reference's `jac_sparsity`, src/python/solve.rs:152-210 and
+ * src/python/sparsity.rs): ivp_rhs_compile_ex plus a pattern of dF/dy in compressed sparse column form -- col_ptr[n + 1],
+ * row_idx[col_ptr[n]]: rows col_ptr[c] .. col_ptr[c + 1] of row_idx are the rows of column c that may be non-zero.  ONE
+ * pattern per compiled problem, shared by every trajectory of a batch.  The forward-difference Jacobian then perturbs
+ * whole GROUPS of columns that share no declared row: n_groups + 1 evaluations of the right-hand side instead of n + 1.
+ *   - Grouping is the reference's first-fit: columns in index order, each into the first group none of whose used rows
+ *     it touches, else a new group (a column without rows joins group 0).  ivp_jac_sparsity_groups() returns it; it is a
+ *     pure host function (no context, no device).
+ *   - A pattern that contains every structurally non-zero entry gives the dense forward differences' matrix -- and so
+ *     every result of the solve -- bit for bit, in both arithmetic modes, as long as the right-hand side stays finite.
+ *     Entries outside the pattern are never written (they stay 0).  An under-declared pattern gives an approximate
+ *     Jacobian, as in the reference: still deterministic, no longer equal to the dense solve.
+ *   - IVP_ERR_BAD_ARGUMENT unless col_ptr[0] == 0, col_ptr is non-decreasing, every row index is in [0, n) and
+ *     8 < n <= 512.  Duplicate rows within a column are accepted.
+ *   - With IVP_RHS_HAS_JAC the snippet's jac_col wins and the pattern is ignored (ivp_wrapper.rs:245-258).
+ *   - The pattern is compiled into the BDF code objects as constant tables: 2 n (n_groups + 1) bytes (3 KB for a
+ *     tridiagonal system at n = 512; 512 KB in the worst case, n = 512 with n groups).  Explicit methods ignore it.
+ */
+int ivp_jac_sparsity_groups(int32_t n, const int32_t *col_ptr, const int32_t *row_idx, int32_t *groups_out /* [n] */, int32_t *n_groups_out);
+int ivp_rhs_compile_sparse(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags,
+                           const int32_t *col_ptr, const int32_t *row_idx, void **handle);
+
 #ifdef __cplusplus
 }
 #endif

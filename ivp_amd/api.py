@@ -304,14 +304,20 @@ class DeviceIVP(IVP):
     rhs_id = 1000
 
     def __init__(self, source: str, n: int, params: Sequence[float] = (), ctx: "Context" = None,
-                 events: Sequence[EventConfig] = (), jac: bool = False):
+                 events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None):
         """``events``: one EventConfig per event function; ``source`` must then also define
         ``__device__ void events(double x, const double* y, double* g, const double* p)``.
         ``jac=True``: ``source`` also overrides the trait's Jacobian (src/ivp.rs:67-107), used by BDF in place of the
         default forward differences: ``__device__ void jac(double x, const double* y, double* j, const double* p)``
         with ``j[row * n + col]`` for n <= 8; for larger systems the column form
         ``__device__ void jac_col(int col, double x, const double* y, double* column, const double* p)``.  Entries the
-        override never writes are zero (the reference's Matrix starts zeroed)."""
+        override never writes are zero (the reference's Matrix starts zeroed).
+        ``jac_sparsity`` (``8 < n <= 512``, read by BDF; the reference's ``jac_sparsity``, src/python/sparsity.rs): the
+        pattern of dF/dy -- anything with ``.tocsc()`` (scipy.sparse), a dense ``(n, n)`` array-like whose non-zeros are
+        the pattern, or a ``(col_ptr, row_idx)`` pair in compressed sparse column form.  The forward-difference Jacobian
+        then perturbs groups of columns that share no declared row (first-fit, ``jac_sparsity_groups``): n_groups + 1
+        right-hand sides instead of n + 1.  A pattern that covers every structural non-zero gives the dense solve's
+        results bit for bit; ``jac=True`` wins over it; explicit methods ignore it."""
         self.source = source
         self.n = int(n)
         self._params = tuple(float(v) for v in params)
@@ -323,12 +329,20 @@ class DeviceIVP(IVP):
         # a second DeviceIVP with the same text -- pyfront.solve_ivp builds one per call, as the reference's Python
         # front end wraps its callable per call -- reuses them instead of compiling again.  Records live as long as the
         # process (a few hundred bytes of host state plus the loaded code objects).
-        key = (source, self.n, self.n_params, len(self._events), bool(jac))
+        pattern = None if jac_sparsity is None else sparsity_csc(jac_sparsity, self.n)
+        key = (source, self.n, self.n_params, len(self._events), bool(jac),
+               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()))
         h = _rhs_records.get(key)
         if h is None:
             h = C.c_void_p()
-            rc = self._ctx.lib.ivp_rhs_compile_ex(self._ctx.handle, source.encode(), self.n, self.n_params,
-                                                  len(self._events), 1 if jac else 0, C.byref(h))
+            if pattern is None:
+                rc = self._ctx.lib.ivp_rhs_compile_ex(self._ctx.handle, source.encode(), self.n, self.n_params,
+                                                      len(self._events), 1 if jac else 0, C.byref(h))
+            else:
+                i32p = C.POINTER(C.c_int32)
+                rc = self._ctx.lib.ivp_rhs_compile_sparse(self._ctx.handle, source.encode(), self.n, self.n_params,
+                                                          len(self._events), 1 if jac else 0, pattern[0].ctypes.data_as(i32p),
+                                                          pattern[1].ctypes.data_as(i32p), C.byref(h))
             if rc != 0:
                 raise ConfigError(rc, self._ctx.last_error())
             _rhs_records[key] = h
@@ -344,7 +358,51 @@ class DeviceIVP(IVP):
         return self._events[index]
 
 
-_rhs_records: dict = {}   # (source, n, n_params, n_events, jac) -> ivp_rhs_compile_ex handle
+_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern) -> ivp_rhs_compile_ex / _sparse handle
+
+
+def sparsity_csc(jac_sparsity, n: int):
+    """``(col_ptr[n + 1], row_idx[nnz])`` as contiguous int32 arrays from any accepted form of ``jac_sparsity``: an object
+    with ``.tocsc()`` (its ``indptr`` / ``indices``, as src/python/sparsity.rs:30-81 reads them), a ``(col_ptr, row_idx)``
+    pair, or a dense ``(n, n)`` array-like whose non-zero entries are the pattern.  The values are checked by the
+    library (``ivp_jac_sparsity_groups`` / ``ivp_rhs_compile_sparse``), only the shapes here."""
+    if hasattr(jac_sparsity, "tocsc"):
+        m = jac_sparsity.tocsc()
+        if tuple(m.shape) != (n, n):
+            raise ValueError(f"jac_sparsity must be ({n}, {n}), got {tuple(m.shape)}")
+        col_ptr, row_idx = m.indptr, m.indices
+    elif isinstance(jac_sparsity, tuple) and len(jac_sparsity) == 2 and np.ndim(jac_sparsity[0]) == 1 and len(jac_sparsity[0]) == n + 1:
+        col_ptr, row_idx = jac_sparsity
+    else:
+        dense = np.asarray(jac_sparsity)
+        if dense.shape != (n, n):
+            raise ValueError(f"jac_sparsity must be ({n}, {n}), a (col_ptr, row_idx) pair or a sparse matrix; got shape {dense.shape}")
+        rows, cols = np.nonzero(dense.T)[::-1]   # column-major order: columns ascending, rows ascending within a column
+        col_ptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=n))))
+        row_idx = rows
+    col_ptr = np.ascontiguousarray(np.asarray(col_ptr).astype(np.int64))
+    row_idx = np.ascontiguousarray(np.asarray(row_idx).astype(np.int64)).reshape(-1)
+    if col_ptr.shape != (n + 1,):
+        raise ValueError(f"jac_sparsity: col_ptr must have n + 1 = {n + 1} entries")
+    if col_ptr.size and int(col_ptr[-1]) != row_idx.size:
+        raise ValueError("jac_sparsity: col_ptr[n] must equal len(row_idx)")
+    if np.abs(col_ptr).max(initial=0) >= 2**31 or np.abs(row_idx).max(initial=0) >= 2**31:
+        raise ValueError("jac_sparsity: indices must fit int32")
+    return col_ptr.astype(np.int32), row_idx.astype(np.int32) if row_idx.size else np.zeros(0, dtype=np.int32)
+
+
+def jac_sparsity_groups(jac_sparsity, n: int):
+    """``(groups, n_groups)``: the column group of every column under the reference's first-fit rule
+    (``ivp_jac_sparsity_groups``; host only, no GPU needed).  Raises ``ConfigError`` for a malformed pattern."""
+    col_ptr, row_idx = sparsity_csc(jac_sparsity, n)
+    groups = np.zeros(n, dtype=np.int32)
+    ng = C.c_int32(0)
+    i32p = C.POINTER(C.c_int32)
+    keep = row_idx if row_idx.size else np.zeros(1, dtype=np.int32)
+    rc = _lib.load().ivp_jac_sparsity_groups(n, col_ptr.ctypes.data_as(i32p), keep.ctypes.data_as(i32p), groups.ctypes.data_as(i32p), C.byref(ng))
+    if rc != 0:
+        raise ConfigError(rc, "invalid jac_sparsity pattern")
+    return groups, int(ng.value)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -136,6 +136,76 @@ struct BdfG {
         __syncthreads();
     }
 
+    // Grouped forward differences from a declared sparsity pattern (src/python/sparsity.rs:160-202, the reference's
+    // `jac_sparsity`): columns that share no declared row are perturbed TOGETHER, so one evaluation of the right-hand
+    // side yields a whole group of columns -- n_groups + 1 evaluations instead of n + 1 (3 + 1 for a tridiagonal system
+    // of any size).  The functor carries the host's first-fit grouping as constant tables (ivp_jit.cpp):
+    //   R::SP_NGROUPS, R::sp_group_of(col), R::sp_hit(g * n + row) = the one column of group g whose declared rows
+    //   contain `row`, or -1.
+    // Same shape as fd_jac: KJ perturbed copies of the state in LDS per sweep, three barriers per sweep -- but a sweep
+    // covers KJ GROUPS.  In copy k every lane perturbs the components it owns whose group is g0 + k (the owner has y[c]
+    // in a register: no shuffles); after the barrier every lane walks its rows, looks the column up in `hit` and stores
+    // (f_row(copy k) - f_row(y)) / pert(col), with pert(col) taken from one more, unperturbed, copy of the state.  Each
+    // declared entry sees the operations of fd_jac on the same operands (perturbation, difference, quotient: no fused
+    // site, so strict and FMA mode agree), hence a pattern that contains every structurally non-zero entry reproduces
+    // fd_jac's matrix bit for bit as long as the right-hand side is finite; entries outside the pattern are never
+    // written and keep the +0.0 the matrix starts with (bdf.rs:152; bdf_group_init_body zeroes it).
+    template <bool LDSWORK>
+    static __device__ __forceinline__ void fd_jac_sparse(double x, const double (&y)[C], const double *p, double *jac, double *work)
+    {
+        static_assert(!LDSWORK || NT >= KJ + 1, "the factor matrix (n x n) must hold KJ + 1 state copies");
+        constexpr int NG = R::SP_NGROUPS;
+        double *st = work;
+        if constexpr (!LDSWORK) {
+            __shared__ double ivp_fds_states[NGROUP * (KJ + 1) * NT];
+            st = ivp_fds_states + (size_t)((int)threadIdx.x / G) * (KJ + 1) * NT;
+        }
+        double fo[C];
+        GR::ode(x, y, fo, p);
+        const double eps = 1.4901161193847656e-08;   // f64::EPSILON.sqrt() = 2^-26
+        int gof[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) gof[c] = own(c) ? (int)R::sp_group_of(gi(c)) : -1;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k <= KJ; ++k)   // copy KJ stays unperturbed
+#pragma unroll
+            for (int c = 0; c < C; ++c) if (own(c)) st[k * NT + gi(c)] = y[c];
+#pragma unroll 1
+        for (int g0 = 0; g0 < NG; g0 += KJ) {
+#pragma unroll
+            for (int k = 0; k < KJ; ++k)
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    if (gof[c] == g0 + k) st[k * NT + gi(c)] = y[c] + eps * fmax(fabs(y[c]), 1.0);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < KJ; ++k) {
+                if (g0 + k < NG) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const int i = gi(c);
+                        if (i < NT) {
+                            const int col = (int)R::sp_hit((g0 + k) * NT + i);
+                            if (col >= 0) {
+                                const double pert = eps * fmax(fabs(st[KJ * NT + col]), 1.0);
+                                jac[(size_t)col * NT + i] = (R::ode_comp(i, x, st + k * NT, p) - fo[c]) / pert;
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            // the copies return to y for the next KJ groups
+#pragma unroll
+            for (int k = 0; k < KJ; ++k)
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    if (gof[c] == g0 + k) st[k * NT + gi(c)] = y[c];
+        }
+        __syncthreads();
+    }
+
     // f.jac(x, y, &mut j): the problem's own Jacobian when the functor has one -- the `impl IVP { fn jac }` override of
     // src/ivp.rs:67-107 in COLUMN form, static void jac_col(int col, double x, const double* y, double* column /* [n] */,
     // const double* p), which writes column `col` of dF/dy (entries it does not write keep their previous value: the
@@ -145,6 +215,12 @@ struct BdfG {
     struct HasJacCol { enum { v = 0 }; };
     template <class RR>
     struct HasJacCol<RR, decltype((void)&RR::jac_col)> { enum { v = 1 }; };
+    // ... and a functor that carries a sparsity pattern (SP_NGROUPS and the tables fd_jac_sparse reads) gets the grouped
+    // differences.  Order: the user's jac_col, then the pattern, then fd_jac (ivp_wrapper.rs:245-258: a given jac wins).
+    template <class RR, class = void>
+    struct HasSparsity { enum { v = 0 }; };
+    template <class RR>
+    struct HasSparsity<RR, decltype((void)RR::SP_NGROUPS)> { enum { v = 1 }; };
     template <bool LDSWORK = false>
     static __device__ __forceinline__ void eval_jac(double x, const double (&y)[C], const double *p, double *jac, double *work = nullptr)
     {
@@ -156,6 +232,8 @@ struct BdfG {
             __syncthreads();
             for (int col = gl(); col < NT; col += G) R::jac_col(col, x, st, jac + (size_t)col * NT, p);
             __syncthreads();
+        } else if constexpr (HasSparsity<R>::v) {
+            fd_jac_sparse<LDSWORK>(x, y, p, jac, work);
         } else {
             fd_jac<LDSWORK>(x, y, p, jac, work);
         }
@@ -594,7 +672,7 @@ __device__ __forceinline__ int32_t bdf_group_init_body(const IvpKArgs &a, uint32
     const double hmax = fabs(a.has_max_step ? a.max_step : fabs(L.xend - L.x0));
     GR::ode(L.x0, y, f0, L.p);
     double *jac = a.bdf_jac + (size_t)j * NT * NT;
-    if constexpr (BG::template HasJacCol<R>::v) {   // the reference's jac storage starts zeroed (bdf.rs:152)
+    if constexpr (BG::template HasJacCol<R>::v || BG::template HasSparsity<R>::v) {   // the reference's jac storage starts zeroed (bdf.rs:152)
         for (int e = BG::gl(); e < NT * NT; e += G) jac[e] = 0.0;
     }
     BG::eval_jac(L.x0, y, L.p, jac);

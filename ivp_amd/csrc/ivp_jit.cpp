@@ -7,6 +7,14 @@
 // which is spliced in front of the very same kernel templates the built-in functors use
 // (ivp_kargs.h + rk_core.h + rk_global.h are embedded in the library as text) and compiled for the
 // context's gfx target.  One module per (method, output mode, fp mode) is built on first use.
+//
+// Jacobian sparsity (ivp_rhs_compile_sparse, 8 < n <= 512): the declared pattern is grouped on the host with the
+// reference's first-fit rule (src/python/sparsity.rs:110-154) and travels to the kernel INSIDE the generated source, as
+// constant tables next to the problem's functor -- IvpKArgs does not change.  The BDF modules of such a problem carry
+//     n_groups, group_of[n] (int16) and hit[n_groups * n] (int16: the column of group g that declares `row`, or -1),
+// which BdfG::fd_jac_sparse (bdf_group.h) reads.  Size: 2 n (n_groups + 1) bytes of constant data per code object --
+// 3 KB for a tridiagonal system at n = 512, 512 KB in the worst case (n = 512, every column its own group).  The
+// on-disk cache keys on the generated source, so two patterns never share an entry.
 #include "ivp_jit.h"
 
 #include <hip/hiprtc.h>
@@ -22,7 +30,12 @@
 
 #include "../../include/ivp_hip.h"
 #include "rk_launch.h"
+#include "ivp_ctx.h"
 #include "ivp_jit_sources.inc"
+
+#ifndef IVP_MAX_GROUP_N
+#define IVP_MAX_GROUP_N 512   // largest n of the wave-per-trajectory kernels (ivp_capi.cpp)
+#endif
 
 namespace {
 
@@ -36,6 +49,8 @@ struct JitRhs {
     int device, n, np, ne;
     bool has_jac = false;   // the snippet defines jac(): IVP::jac override (src/ivp.rs:67-107)
     std::string ode_source;
+    std::string sparsity_source;   // the pattern's tables as device code (empty: no pattern, or the snippet has its own jac_col)
+    int n_groups = 0;
     std::string arch;
     std::mutex mu;
     // (device, method, fp_mode, full, ctl): hipModuleLoadData binds a module to the device that is current when it is
@@ -48,6 +63,55 @@ std::string join(const char *const *parts)
 {
     std::string s;
     for (; *parts; ++parts) s += *parts;
+    return s;
+}
+
+// The reference's group_columns (src/python/sparsity.rs:110-154), exactly: columns in index order, each into the FIRST
+// group none of whose used rows it touches, else into a new group (a column without rows lands in group 0).  The order
+// decides which perturbations alias when a caller declares too little, so it is part of the contract.
+// Returns IVP_OK, or IVP_ERR_BAD_ARGUMENT with *why set.  hit (optional) receives [n_groups * n].
+int group_columns(int n, const int32_t *col_ptr, const int32_t *row_idx, std::vector<int32_t> &groups, int *n_groups,
+                  std::vector<int16_t> *hit, const char **why)
+{
+    static const char *dummy;
+    if (!why) why = &dummy;
+    if (n <= IVP_MAX_N || n > IVP_MAX_GROUP_N) { *why = "jac_sparsity needs 8 < n <= 512"; return IVP_ERR_BAD_ARGUMENT; }
+    if (!col_ptr || col_ptr[0] != 0) { *why = "jac_sparsity: col_ptr[0] must be 0"; return IVP_ERR_BAD_ARGUMENT; }
+    for (int c = 0; c < n; ++c)
+        if (col_ptr[c + 1] < col_ptr[c]) { *why = "jac_sparsity: col_ptr must be non-decreasing"; return IVP_ERR_BAD_ARGUMENT; }
+    if (col_ptr[n] > 0 && !row_idx) { *why = "jac_sparsity: row_idx is NULL"; return IVP_ERR_BAD_ARGUMENT; }
+    for (int32_t e = 0; e < col_ptr[n]; ++e)
+        if (row_idx[e] < 0 || row_idx[e] >= n) { *why = "jac_sparsity: row index out of range"; return IVP_ERR_BAD_ARGUMENT; }
+    groups.assign((size_t)n, 0);
+    std::vector<std::vector<int16_t>> used;   // per group: the column that uses the row, or -1
+    for (int c = 0; c < n; ++c) {
+        const int32_t *rows = row_idx + col_ptr[c];
+        const int32_t nr = col_ptr[c + 1] - col_ptr[c];
+        size_t g = 0;
+        for (; g < used.size(); ++g) {
+            bool fits = true;
+            for (int32_t e = 0; e < nr && fits; ++e) fits = used[g][(size_t)rows[e]] < 0;
+            if (fits) break;
+        }
+        if (g == used.size()) used.emplace_back((size_t)n, (int16_t)-1);
+        groups[(size_t)c] = (int32_t)g;
+        for (int32_t e = 0; e < nr; ++e) used[g][(size_t)rows[e]] = (int16_t)c;   // duplicate rows of a column collapse here
+    }
+    *n_groups = (int)used.size();
+    if (hit) {
+        hit->clear();
+        for (const auto &u : used) hit->insert(hit->end(), u.begin(), u.end());
+    }
+    return IVP_OK;
+}
+
+std::string sparsity_tables(int n, const std::vector<int32_t> &groups, int n_groups, const std::vector<int16_t> &hit)
+{
+    std::string s = "namespace ivp_jit {\n__device__ const short ivp_sp_group_of[" + std::to_string(n) + "] = {";
+    for (int c = 0; c < n; ++c) { s += std::to_string(groups[(size_t)c]); s += c + 1 < n ? "," : ""; }
+    s += "};\n__device__ const short ivp_sp_hit[" + std::to_string((size_t)n_groups * n) + "] = {";
+    for (size_t e = 0; e < hit.size(); ++e) { s += std::to_string((int)hit[e]); s += (e + 1) % 32 == 0 ? ",\n" : ","; }
+    s += "};\n}\n";
     return s;
 }
 
@@ -75,6 +139,15 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
         s += join(k_src_rk_global_h);   // compact_append
         s += join(k_src_rk_group_h);
         s += join(k_src_bdf_group_h);
+        // the pattern is read by BDF only (the explicit methods never call jac): other modules compile to what they were
+        const bool sparse = method == IVP_BDF && !r.sparsity_source.empty();
+        std::string sp;
+        if (sparse) {
+            s += r.sparsity_source;
+            sp = "  enum { SP_NGROUPS = " + std::to_string(r.n_groups) + " };\n"
+                 "  static __device__ __forceinline__ int sp_group_of(int c) { return ivp_sp_group_of[c]; }\n"
+                 "  static __device__ __forceinline__ int sp_hit(int e) { return ivp_sp_hit[e]; }\n";
+        }
         std::snprintf(buf, sizeof buf,
                       "namespace ivp_jit { struct RhsUser { enum { N = %d, P = %d, NE = IVP_USER_NE };\n"
                       "  static __device__ __forceinline__ double ode_comp(int i, double x, const double* y, const double* p) { return ::ode_comp(i, x, y, p); }\n"
@@ -84,10 +157,11 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                       "#if IVP_USER_JAC\n"
                       "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
                       "#endif\n"
+                      "%s"
                       "}; }\n"
                       "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<%d, ivp_jit::RhsUser, %s, %d>(a); }\n"
                       "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<%d, ivp_jit::RhsUser, %s, %d>(a); }\n",
-                      r.n, r.np, method, full, ivp_group_width(r.n), method, full, ivp_group_width(r.n));
+                      r.n, r.np, sp.c_str(), method, full, ivp_group_width(r.n), method, full, ivp_group_width(r.n));
         s += buf;
         return s;
     }
@@ -220,9 +294,23 @@ int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitMo
 
 int ivp_jit_n_events(void *handle) { return handle ? ((JitRhs *)handle)->ne : 0; }
 
-int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log)
+int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log,
+                    const int32_t *col_ptr, const int32_t *row_idx)
 {
+    std::string sparsity_source;
+    int n_groups = 0;
+    if (col_ptr) {
+        std::vector<int32_t> groups;
+        std::vector<int16_t> hit;
+        const char *why = "";
+        const int rc = group_columns(n, col_ptr, row_idx, groups, &n_groups, &hit, &why);
+        if (rc != IVP_OK) { if (log) *log = why; return rc; }
+        // a snippet with its own jac_col keeps it and the pattern is dropped (ivp_wrapper.rs:245-258)
+        if (!(flags & IVP_RHS_HAS_JAC)) sparsity_source = sparsity_tables(n, groups, n_groups, hit);
+    }
     JitRhs *r = new JitRhs();
+    r->sparsity_source = sparsity_source;
+    r->n_groups = n_groups;
     r->device = device;
     r->has_jac = (flags & IVP_RHS_HAS_JAC) != 0;
     r->n = n;
@@ -312,3 +400,34 @@ hipError_t ivp_jit_launch(void *handle, int what, int method, int fp_mode, int f
     void *args[] = {&ka};
     return hipModuleLaunchKernel(fn, grid, grid_y, 1, IVP_WAVE, 1, 1, 0, s, args, nullptr);
 }
+
+extern "C" {
+
+int ivp_jac_sparsity_groups(int32_t n, const int32_t *col_ptr, const int32_t *row_idx, int32_t *groups_out, int32_t *n_groups_out)
+{
+    if (!groups_out || !n_groups_out) return IVP_ERR_BAD_ARGUMENT;
+    std::vector<int32_t> groups;
+    int n_groups = 0;
+    const int rc = group_columns(n, col_ptr, row_idx, groups, &n_groups, nullptr, nullptr);
+    if (rc != IVP_OK) return rc;
+    for (int32_t c = 0; c < n; ++c) groups_out[c] = groups[(size_t)c];
+    *n_groups_out = n_groups;
+    return IVP_OK;
+}
+
+int ivp_rhs_compile_sparse(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags,
+                           const int32_t *col_ptr, const int32_t *row_idx, void **handle)
+{
+    using ivp_host::fail;
+    if (!ctx || !source || !handle) return IVP_ERR_BAD_ARGUMENT;
+    if (n < 1 || n > IVP_MAX_GROUP_N || n_params < 0 || n_params > IVP_MAX_P || n_events < 0 || n_events > 64)
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
+    if (flags & ~IVP_RHS_HAS_JAC) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if (!col_ptr) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "jac_sparsity: col_ptr is NULL");
+    std::string log;
+    const int rc = ivp_jit_compile(ctx->device, source, n, n_params, n_events, flags, handle, &log, col_ptr, row_idx);
+    if (rc != IVP_OK) ctx->err = log;
+    return rc;
+}
+
+}  // extern "C"

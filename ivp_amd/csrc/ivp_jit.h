@@ -4,7 +4,9 @@
 #include <string>
 #include "ivp_kargs.h"
 
-int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log);
+// col_ptr / row_idx: optional Jacobian sparsity pattern (CSC, one per problem; ivp_rhs_compile_sparse)
+int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log,
+                    const int32_t *col_ptr = nullptr, const int32_t *row_idx = nullptr);
 int ivp_jit_n_events(void *handle);
 void ivp_jit_free(void *handle);
 void ivp_jit_dims(void *handle, int *n, int *n_params);

@@ -22,6 +22,12 @@ the arithmetic; for a large system whose components are cheap on their own defin
 expression of ``x``, ``y``, ``p`` whose sign changes are located, with the ``terminal`` / ``direction`` attributes the
 reference reads off the Python event functions (solve.rs:246-289).  ``jac``: a string with the statements filling
 ``j[row * n + col]``, or a constant matrix (njev is then reported as 0, solve.rs:216-218).
+
+``jac_sparsity`` (string right-hand sides with more than 8 states, ``method="BDF"``): the pattern of dF/dy as a scipy
+sparse matrix, a dense array-like or a ``(col_ptr, row_idx)`` pair; the forward-difference Jacobian then costs one
+right-hand side per column GROUP (solve.rs:152-210, sparsity.rs).  A pattern that covers every structural non-zero gives
+exactly the results of the solve without it.  A given ``jac`` wins; explicit methods accept and ignore it; for n <= 8
+(thread-per-trajectory kernels, at most 8 columns to save) it raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -139,7 +145,7 @@ def _event_config(ev) -> api.EventConfig:
     return cfg
 
 
-def _device_problem(fun: str, n: int, args, events: list, jac, ctx) -> api.DeviceIVP:
+def _device_problem(fun: str, n: int, args, events: list, jac, ctx, jac_sparsity=None) -> api.DeviceIVP:
     if "__device__" in fun:
         src = fun
     elif n <= api.MAX_LANE_N:
@@ -190,7 +196,8 @@ def _device_problem(fun: str, n: int, args, events: list, jac, ctx) -> api.Devic
                     "__device__ void jac_col(int ivp_c, double x, const double* y, double* column, const double* p) {\n"
                     f"  for (int r = 0; r < {n}; ++r) column[r] = 0.0;\n  ivp_jac_proxy j{{column, ivp_c, 0.0}};\n" + jbody + "\n}\n")
     params = () if args is None else tuple(float(a) for a in (args if isinstance(args, (tuple, list)) else (args,)))
-    return api.DeviceIVP(src, n, params, ctx=ctx, events=[_event_config(e) for e in events], jac=has_jac)
+    extra = {} if (has_jac or jac_sparsity is None) else {"jac_sparsity": jac_sparsity}   # a given jac wins (ivp_wrapper.rs:245-258)
+    return api.DeviceIVP(src, n, params, ctx=ctx, events=[_event_config(e) for e in events], jac=has_jac, **extra)
 
 
 def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, dense_output: bool = False, events=None,
@@ -199,12 +206,13 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
     """``ivp.solve_ivp`` (src/python/solve.rs:150-222).  Recognised ``options``: rtol, atol (scalar or per-component),
     max_step, min_step, first_step, max_steps (solve.rs:292-340); like the reference, other keys are ignored."""
     del vectorized   # accepted and unused, as in the reference (solve.rs:166)
-    if jac_sparsity is not None:
-        # the reference groups finite-difference columns by the sparsity pattern (src/python/sparsity.rs); the
-        # device BDF differences a dense n <= 8 Jacobian column by column -- refusing beats silently different nfev
-        raise NotImplementedError("jac_sparsity is not supported on the GPU path (dense Jacobians only)")
     t0, tf = (float(v) for v in t_span)
     y0v = np.atleast_1d(np.asarray(y0, dtype=np.float64))
+    if jac_sparsity is not None and (y0v.size <= api.MAX_LANE_N or not isinstance(fun, str)):
+        # the reference groups finite-difference columns by the sparsity pattern (src/python/sparsity.rs); the
+        # device BDF differences a dense n <= 8 Jacobian column by column -- refusing beats silently different nfev
+        raise NotImplementedError("jac_sparsity is supported for string right-hand sides with more than 8 states "
+                                  "(the register-resident n <= 8 path differences dense Jacobians only)")
     ev = _event_list(events)
     if isinstance(fun, api.IVP):
         if args is not None:
@@ -222,7 +230,8 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
             # the explicit methods never call the Jacobian (the reference accepts and ignores it there)
             uses_jac = isinstance(method, str) and api.Method.from_str(method) == api.Method.BDF
             try:
-                problem = _device_problem(fun, y0v.size, args, ev, jac if uses_jac else None, ctx)
+                # ... and so never read the sparsity pattern either
+                problem = _device_problem(fun, y0v.size, args, ev, jac if uses_jac else None, ctx, jac_sparsity if uses_jac else None)
             except api.IvpError as e:   # a snippet that does not compile surfaces like any other solver failure (solve.rs:216-221)
                 raise RuntimeError(f"Solver failed: {e}") from e
         has_events = events is not None

@@ -287,4 +287,9 @@ extern "C" {
     pub fn ivp_rhs_compile_ex(ctx: *mut ivp_ctx_t, source: *const c_char, n: i32, n_params: i32, n_events: i32, flags: u32,
                               handle: *mut *mut c_void) -> c_int;
     pub fn ivp_rhs_free(handle: *mut c_void);
+    // `jac_sparsity` (src/python/sparsity.rs): first-fit column groups of a CSC pattern (pure host), and a right-hand side
+    // whose BDF Jacobian is differenced group by group (8 < n <= 512)
+    pub fn ivp_jac_sparsity_groups(n: i32, col_ptr: *const i32, row_idx: *const i32, groups_out: *mut i32, n_groups_out: *mut i32) -> c_int;
+    pub fn ivp_rhs_compile_sparse(ctx: *mut ivp_ctx_t, source: *const c_char, n: i32, n_params: i32, n_events: i32, flags: u32,
+                                  col_ptr: *const i32, row_idx: *const i32, handle: *mut *mut c_void) -> c_int;
 }
