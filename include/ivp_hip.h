@@ -633,7 +633,27 @@ void ivp_rhs_free(void *handle);
  *   - With IVP_RHS_HAS_JAC the snippet's jac_col wins and the pattern is ignored (ivp_wrapper.rs:245-258).
  *   - The pattern is compiled into the BDF code objects as constant tables: 2 n (n_groups + 1) bytes (3 KB for a
  *     tridiagonal system at n = 512; 512 KB in the worst case, n = 512 with n groups).  Explicit methods ignore it.
+ *
+ * Banded storage: flags & IVP_RHS_BANDED (ivp_rhs_compile_sparse only) is the reference's
+ * `jac_storage = MatrixStorage::Banded{ml, mu}` (src/solve/options.rs:104-108) with ml = max(row - col) and
+ * mu = max(col - row) over the declared entries (ivp_jac_sparsity_bandwidth(): pure host, same validation and error codes
+ * as ivp_jac_sparsity_groups(); an empty or diagonal pattern gives (0, 0)).  BDF then stores J and the factors of
+ * (I - cJ) by bands and factorises / solves with banded kernels whose factors stay in LDS whenever they fit.
+ *   - Layout (LAPACK general band, column-major, one contiguous block per trajectory): J entry (i, j) at
+ *     j (ml + mu + 1) + (mu + i - j); factor entry (i, j), j - ml - mu <= i <= j + ml, at j W + (ml + mu + i - j) with
+ *     W = 2 ml + mu + 1 (the ml extra superdiagonals take the fill of row exchanges).  ivp_rhs_jac_layout() reports the
+ *     per-trajectory sizes of any compiled problem: n n twice (dense), or (ml + mu + 1) n and (2 ml + mu + 1) n.
+ *   - Contract: for a finite right-hand side and a pattern that contains every structurally non-zero entry, every result
+ *     of the solve equals the dense solve with the same pattern bit for bit, in both arithmetic modes and for any chunk
+ *     length.  Outside the claim: the sign of a zero (the dense solves add (+-0) b[k] to out-of-band rows, which turns a
+ *     -0.0 there into +0.0; banded leaves it) and non-finite values (0 * inf outside the band).
+ *   - IVP_ERR_BAD_ARGUMENT (message in ivp_last_error_string) when n <= 8, when combined with IVP_RHS_HAS_JAC (an
+ *     analytic jac_col in band storage is not supported), and when 2 ml + mu + 1 >= n (the band is as wide as the matrix).
+ *   - ivp_options_t.variant == 1 keeps the banded factors in global memory; 0 and 2 keep them in LDS when they fit.
  */
+#define IVP_RHS_BANDED 2u
+int ivp_jac_sparsity_bandwidth(int32_t n, const int32_t *col_ptr, const int32_t *row_idx, int32_t *ml_out, int32_t *mu_out);
+int ivp_rhs_jac_layout(const void *handle, int32_t *banded, int32_t *ml, int32_t *mu, uint64_t *jac_doubles, uint64_t *lu_doubles);
 int ivp_jac_sparsity_groups(int32_t n, const int32_t *col_ptr, const int32_t *row_idx, int32_t *groups_out /* [n] */, int32_t *n_groups_out);
 int ivp_rhs_compile_sparse(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags,
                            const int32_t *col_ptr, const int32_t *row_idx, void **handle);

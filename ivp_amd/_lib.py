@@ -95,6 +95,7 @@ EXPORTS = (
     "ivp_ctx_get_stats", "ivp_options_default", "ivp_options_method_defaults", "ivp_rhs_dims", "ivp_rhs_n_events", "ivp_batch_solve",
     "ivp_batch_solve_device", "ivp_batch_submit_device", "ivp_batch_poll", "ivp_batch_wait", "ivp_batch_solve_multi", "ivp_batch_solve_multi_host",
     "ivp_rhs_compile", "ivp_rhs_compile_events", "ivp_rhs_compile_ex", "ivp_rhs_free", "ivp_jac_sparsity_groups", "ivp_rhs_compile_sparse",
+    "ivp_jac_sparsity_bandwidth", "ivp_rhs_jac_layout",
     "ivp_batch_solve_logged", "ivp_batch_solve_logged_device", "ivp_step_log_fetch_device", "ivp_step_log_free", "ivp_batch_solve_logged_multi", "ivp_step_log_fetch_multi",
     "ivp_batch_solve_dense_device", "ivp_batch_solve_dense", "ivp_dense_log_fetch_device", "ivp_dense_log_free", "ivp_dense_eval_device",
     "ivp_batch_solve_events_device", "ivp_batch_solve_events", "ivp_event_log_fetch_device", "ivp_event_log_free",
@@ -212,6 +213,10 @@ def load():
     L.ivp_jac_sparsity_groups.argtypes = [C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p]
     L.ivp_rhs_compile_sparse.restype = C.c_int
     L.ivp_rhs_compile_sparse.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]
+    L.ivp_jac_sparsity_bandwidth.restype = C.c_int
+    L.ivp_jac_sparsity_bandwidth.argtypes = [C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p]
+    L.ivp_rhs_jac_layout.restype = C.c_int
+    L.ivp_rhs_jac_layout.argtypes = [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.ivp_rhs_n_events.restype = C.c_int
     L.ivp_rhs_n_events.argtypes = [C.c_int32]
     L.ivp_rhs_free.restype = None

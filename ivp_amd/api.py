@@ -304,7 +304,7 @@ class DeviceIVP(IVP):
     rhs_id = 1000
 
     def __init__(self, source: str, n: int, params: Sequence[float] = (), ctx: "Context" = None,
-                 events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None):
+                 events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None, jac_storage: str = "full"):
         """``events``: one EventConfig per event function; ``source`` must then also define
         ``__device__ void events(double x, const double* y, double* g, const double* p)``.
         ``jac=True``: ``source`` also overrides the trait's Jacobian (src/ivp.rs:67-107), used by BDF in place of the
@@ -317,7 +317,17 @@ class DeviceIVP(IVP):
         the pattern, or a ``(col_ptr, row_idx)`` pair in compressed sparse column form.  The forward-difference Jacobian
         then perturbs groups of columns that share no declared row (first-fit, ``jac_sparsity_groups``): n_groups + 1
         right-hand sides instead of n + 1.  A pattern that covers every structural non-zero gives the dense solve's
-        results bit for bit; ``jac=True`` wins over it; explicit methods ignore it."""
+        results bit for bit; ``jac=True`` wins over it; explicit methods ignore it.
+        ``jac_storage="banded"`` (needs a pattern, not with ``jac=True``; the reference's ``MatrixStorage::Banded{ml, mu}``):
+        BDF stores J and the factors of (I - cJ) by bands, with the bandwidths of the pattern (``jac_bandwidth``), and
+        factorises and solves with the banded kernels -- same results bit for bit, (3 ml + 2 mu + 2) n doubles per
+        trajectory instead of 2 n^2 (``jac_layout``).  The default ``"full"`` is the n x n storage."""
+        if jac_storage not in ("full", "banded"):
+            raise ValueError(f'jac_storage must be "full" or "banded", got {jac_storage!r}')
+        if jac_storage == "banded" and jac_sparsity is None:
+            raise ValueError('jac_storage="banded" needs a jac_sparsity pattern: the bandwidths are taken from it')
+        if jac_storage == "banded" and jac:
+            raise ValueError('jac_storage="banded" with jac=True: an analytic jac_col in band storage is not supported')
         self.source = source
         self.n = int(n)
         self._params = tuple(float(v) for v in params)
@@ -331,7 +341,7 @@ class DeviceIVP(IVP):
         # process (a few hundred bytes of host state plus the loaded code objects).
         pattern = None if jac_sparsity is None else sparsity_csc(jac_sparsity, self.n)
         key = (source, self.n, self.n_params, len(self._events), bool(jac),
-               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()))
+               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()), jac_storage)
         h = _rhs_records.get(key)
         if h is None:
             h = C.c_void_p()
@@ -341,7 +351,8 @@ class DeviceIVP(IVP):
             else:
                 i32p = C.POINTER(C.c_int32)
                 rc = self._ctx.lib.ivp_rhs_compile_sparse(self._ctx.handle, source.encode(), self.n, self.n_params,
-                                                          len(self._events), 1 if jac else 0, pattern[0].ctypes.data_as(i32p),
+                                                          len(self._events), (1 if jac else 0) | (RHS_BANDED if jac_storage == "banded" else 0),
+                                                          pattern[0].ctypes.data_as(i32p),
                                                           pattern[1].ctypes.data_as(i32p), C.byref(h))
             if rc != 0:
                 raise ConfigError(rc, self._ctx.last_error())
@@ -357,8 +368,21 @@ class DeviceIVP(IVP):
     def event_config(self, index):
         return self._events[index]
 
+    @property
+    def jac_layout(self) -> dict:
+        """Per-trajectory storage of the BDF matrices of this compiled problem (``ivp_rhs_jac_layout``):
+        ``{"banded", "ml", "mu", "jac_doubles", "lu_doubles"}``."""
+        banded, ml, mu = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        jd, ld = C.c_uint64(0), C.c_uint64(0)
+        rc = self._ctx.lib.ivp_rhs_jac_layout(self.handle, C.byref(banded), C.byref(ml), C.byref(mu), C.byref(jd), C.byref(ld))
+        if rc != 0:
+            raise ConfigError(rc, "ivp_rhs_jac_layout")
+        return {"banded": bool(banded.value), "ml": int(ml.value), "mu": int(mu.value),
+                "jac_doubles": int(jd.value), "lu_doubles": int(ld.value)}
 
-_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern) -> ivp_rhs_compile_ex / _sparse handle
+
+RHS_BANDED = 2   # IVP_RHS_BANDED (include/ivp_hip.h)
+_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern, jac_storage) -> ivp_rhs_compile_ex / _sparse handle
 
 
 def sparsity_csc(jac_sparsity, n: int):
@@ -403,6 +427,20 @@ def jac_sparsity_groups(jac_sparsity, n: int):
     if rc != 0:
         raise ConfigError(rc, "invalid jac_sparsity pattern")
     return groups, int(ng.value)
+
+
+def jac_bandwidth(jac_sparsity, n: int):
+    """``(ml, mu)``: the lower and upper bandwidth of a pattern, ``max(row - col)`` and ``max(col - row)`` over its declared
+    entries (``ivp_jac_sparsity_bandwidth``; host only, no GPU needed) -- what ``jac_storage="banded"`` stores.  Raises
+    ``ConfigError`` for a malformed pattern."""
+    col_ptr, row_idx = sparsity_csc(jac_sparsity, n)
+    ml, mu = C.c_int32(0), C.c_int32(0)
+    i32p = C.POINTER(C.c_int32)
+    keep = row_idx if row_idx.size else np.zeros(1, dtype=np.int32)
+    rc = _lib.load().ivp_jac_sparsity_bandwidth(n, col_ptr.ctypes.data_as(i32p), keep.ctypes.data_as(i32p), C.byref(ml), C.byref(mu))
+    if rc != 0:
+        raise ConfigError(rc, "invalid jac_sparsity pattern")
+    return int(ml.value), int(mu.value)
 
 
 # ------------------------------------------------------------------------------------------------

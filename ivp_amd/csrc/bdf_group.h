@@ -45,6 +45,24 @@ __device__ unsigned long long ivp_phase_clk[16];
 #define IVP_CLK(ph) do { } while (0)
 #endif
 
+// Banded storage (bdf_band.h, included after this header): a functor that carries SP_ML / SP_MU keeps J and the factors of
+// (I - cJ) by bands and is factorised and solved by BdfBand<R, G>.  Every hook below is an `if constexpr` on HasBand<R>::v:
+// functors without the two constants compile to exactly what they compiled to before.
+template <class RR, class = void>
+struct HasBand { enum { v = 0 }; };
+template <class RR>
+struct HasBand<RR, decltype((void)RR::SP_ML)> { enum { v = 1 }; };
+template <class R, int G>
+struct BdfBand;
+// static LDS budget of a banded BDF kernel with resident factors: the limit of a static __shared__ allocation (64 KiB),
+// which also leaves room for two such workgroups on a CU (160 KiB)
+#define IVP_BAND_LDS_BUDGET 65536
+// doubles per trajectory of the J block and of the factor block
+template <class R>
+constexpr int bdf_jac_doubles() { if constexpr (HasBand<R>::v) return (R::SP_ML + R::SP_MU + 1) * R::N; else return R::N * R::N; }
+template <class R>
+constexpr int bdf_lu_doubles() { if constexpr (HasBand<R>::v) return (2 * R::SP_ML + R::SP_MU + 1) * R::N; else return R::N * R::N; }
+
 template <class R, int G>
 struct BdfG {
     using GR = GroupRhs<R, G>;
@@ -150,6 +168,13 @@ struct BdfG {
     // site, so strict and FMA mode agree), hence a pattern that contains every structurally non-zero entry reproduces
     // fd_jac's matrix bit for bit as long as the right-hand side is finite; entries outside the pattern are never
     // written and keep the +0.0 the matrix starts with (bdf.rs:152; bdf_group_init_body zeroes it).
+    // where entry (row, col) of J lives in the band layout of bdf_band.h (declared entries are in band by construction: the
+    // bandwidths are taken from the pattern)
+    static __device__ __forceinline__ size_t jac_at(int row, int col)
+    {
+        if constexpr (HasBand<R>::v) return (size_t)col * (R::SP_ML + R::SP_MU + 1) + (size_t)(R::SP_MU + row - col);
+        else return (size_t)col * NT + row;
+    }
     template <bool LDSWORK>
     static __device__ __forceinline__ void fd_jac_sparse(double x, const double (&y)[C], const double *p, double *jac, double *work)
     {
@@ -189,7 +214,8 @@ struct BdfG {
                             const int col = (int)R::sp_hit((g0 + k) * NT + i);
                             if (col >= 0) {
                                 const double pert = eps * fmax(fabs(st[KJ * NT + col]), 1.0);
-                                jac[(size_t)col * NT + i] = (R::ode_comp(i, x, st + k * NT, p) - fo[c]) / pert;
+                                if constexpr (HasBand<R>::v) jac[jac_at(i, col)] = (R::ode_comp(i, x, st + k * NT, p) - fo[c]) / pert;
+                                else jac[(size_t)col * NT + i] = (R::ode_comp(i, x, st + k * NT, p) - fo[c]) / pert;
                             }
                         }
                     }
@@ -672,7 +698,10 @@ __device__ __forceinline__ int32_t bdf_group_init_body(const IvpKArgs &a, uint32
     const double hmax = fabs(a.has_max_step ? a.max_step : fabs(L.xend - L.x0));
     GR::ode(L.x0, y, f0, L.p);
     double *jac = a.bdf_jac + (size_t)j * NT * NT;
-    if constexpr (BG::template HasJacCol<R>::v || BG::template HasSparsity<R>::v) {   // the reference's jac storage starts zeroed (bdf.rs:152)
+    if constexpr (HasBand<R>::v) {   // band block (bdf_band.h): zeroed like the full matrix below
+        jac = a.bdf_jac + (size_t)j * bdf_jac_doubles<R>();
+        for (int e = BG::gl(); e < bdf_jac_doubles<R>(); e += G) jac[e] = 0.0;
+    } else if constexpr (BG::template HasJacCol<R>::v || BG::template HasSparsity<R>::v) {   // the reference's jac storage starts zeroed (bdf.rs:152)
         for (int e = BG::gl(); e < NT * NT; e += G) jac[e] = 0.0;
     }
     BG::eval_jac(L.x0, y, L.p, jac);
@@ -813,7 +842,8 @@ __device__ __forceinline__ bool bdf_group_attempt(const IvpKArgs &a, uint32_t j,
         __syncthreads();
         // (I - cJ), element by element over the n x n column-major block: coalesced, FB loads in flight per lane (a loop
         // over columns waited for one memory round trip per column: 64 000 cycles per refactorisation at n = 100)
-        {
+        if constexpr (HasBand<R>::v) BdfBand<R, G>::form(jac, lu, c);   // ... or over the band block
+        else {
             constexpr int NE = BG::NT * BG::NT, FB = 8;
 #pragma unroll 1
             for (int e0 = 0; e0 < NE; e0 += FB * G) {
@@ -832,7 +862,10 @@ __device__ __forceinline__ bool bdf_group_attempt(const IvpKArgs &a, uint32_t j,
         S.d_nlu += 1;
         IVP_CLK(1);
         // (the first 64 trajectories report how dense their elimination was: a.err_flag[1..2], read by the host every round)
-        if (BG::lu_decomp(lu, piv, j < 64u ? a.err_flag + 1 : nullptr)) { lu_current = true; S.current_c = c; }
+        bool lu_ok;
+        if constexpr (HasBand<R>::v) lu_ok = BdfBand<R, G>::lu_decomp_band(lu, piv);
+        else lu_ok = BG::lu_decomp(lu, piv, j < 64u ? a.err_flag + 1 : nullptr);
+        if (lu_ok) { lu_current = true; S.current_c = c; }
         else lu_failed = true;
         __syncthreads();
         IVP_CLK(2);
@@ -860,7 +893,8 @@ __device__ __forceinline__ bool bdf_group_attempt(const IvpKArgs &a, uint32_t j,
 #pragma unroll
         for (int i = 0; i < C; ++i) rhs[i] = IVP_MB(c, rhs[i], psi[i]) - delta[i];
         IVP_CLK(3);
-        BG::lin_solve(lu, piv, rhs);
+        if constexpr (HasBand<R>::v) BdfBand<R, G>::lin_solve_band(lu, piv, rhs);
+        else BG::lin_solve(lu, piv, rhs);
         IVP_CLK(4);
         const double dy_norm = BG::wrms(rhs, scale);
         IVP_CLK(5);
@@ -1025,8 +1059,11 @@ __device__ __forceinline__ uint32_t bdf_group_chunk_body(const IvpKArgs &a, uint
     using GR = GroupRhs<R, G>;
     using MAP = typename OutMap<GR>::type;
     constexpr int C = BG::C, NT = BG::NT, P = R::P;
-    constexpr bool kLds = LDSLU && BG::NGROUP == 1 && NT <= IVP_LDS_LU_MAX_N;
-    static_assert(!LDSLU || kLds, "LDS-resident factors: one wavefront per trajectory, n <= IVP_LDS_LU_MAX_N");
+    constexpr bool kBand = HasBand<R>::v;
+    constexpr bool kLds = !kBand && LDSLU && BG::NGROUP == 1 && NT <= IVP_LDS_LU_MAX_N;
+    constexpr bool kBandLds = kBand && LDSLU;   // banded factors resident in LDS (bdf_band.h): any group width
+    static_assert(!LDSLU || kLds || kBandLds, "LDS-resident factors: one wavefront per trajectory, n <= IVP_LDS_LU_MAX_N");
+    constexpr int JD = bdf_jac_doubles<R>(), LD = bdf_lu_doubles<R>();
     const size_t B = a.B;
     BdfGLane<C> S;
     Lane<C, P> L;
@@ -1039,6 +1076,7 @@ __device__ __forceinline__ uint32_t bdf_group_chunk_body(const IvpKArgs &a, uint
 #pragma unroll
     for (int c = 0; c < P; ++c) L.p[c] = a.params[c * B + j];
     double *jac = a.bdf_jac + (size_t)j * NT * NT, *lu_mem = a.bdf_lu + (size_t)j * NT * NT;
+    if constexpr (kBand) { jac = a.bdf_jac + (size_t)j * JD; lu_mem = a.bdf_lu + (size_t)j * LD; }
     uint32_t *piv_mem = a.bdf_piv + (size_t)j * NT;
     double *lu = lu_mem;
     uint32_t *piv = piv_mem;
@@ -1055,6 +1093,18 @@ __device__ __forceinline__ uint32_t bdf_group_chunk_body(const IvpKArgs &a, uint
         if (S.flags & IVP_BDF_LU_CURRENT) {   // factors computed by an earlier launch: fetch them (coalesced)
             for (int e = (int)threadIdx.x; e < NT * NT; e += IVP_WAVE) ivp_lu_lds[e] = lu_mem[e];
             for (int e = (int)threadIdx.x; e < NT; e += IVP_WAVE) ivp_piv_lds[e] = piv_mem[e];
+        }
+        __syncthreads();
+    }
+    if constexpr (kBandLds) {
+        static_assert(BdfBand<R, G>::lds_bytes() <= IVP_BAND_LDS_BUDGET, "banded factors do not fit the LDS budget (the host chooses the global form)");
+        __shared__ double ivp_band_lu_lds[BG::NGROUP * LD];
+        __shared__ uint32_t ivp_band_piv_lds[BG::NGROUP * NT];
+        lu = ivp_band_lu_lds + (size_t)((int)threadIdx.x / G) * LD;
+        piv = ivp_band_piv_lds + (size_t)((int)threadIdx.x / G) * NT;
+        if (S.flags & IVP_BDF_LU_CURRENT) {   // factors computed by an earlier launch: fetch them (coalesced)
+            for (int e = BG::gl(); e < LD; e += G) lu[e] = lu_mem[e];
+            for (int e = BG::gl(); e < NT; e += G) piv[e] = piv_mem[e];
         }
         __syncthreads();
     }
@@ -1102,6 +1152,12 @@ __device__ __forceinline__ uint32_t bdf_group_chunk_body(const IvpKArgs &a, uint
         if (S.flags & IVP_BDF_LU_CURRENT) {   // the next launch continues with these factors (same nlu as the global-memory path)
             for (int e = (int)threadIdx.x; e < NT * NT; e += IVP_WAVE) lu_mem[e] = lu[e];
             for (int e = (int)threadIdx.x; e < NT; e += IVP_WAVE) piv_mem[e] = piv[e];
+        }
+    }
+    if constexpr (kBandLds) {
+        if (S.flags & IVP_BDF_LU_CURRENT) {
+            for (int e = BG::gl(); e < LD; e += G) lu_mem[e] = lu[e];
+            for (int e = BG::gl(); e < NT; e += G) piv_mem[e] = piv[e];
         }
     }
 #pragma unroll

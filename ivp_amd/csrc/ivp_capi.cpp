@@ -333,6 +333,8 @@ int enqueue_round(ivp_ctx *ctx)
         // dense their eliminations are (the two words behind err_flag); once more than half of the trailing columns a pivot
         // looks at need an update the LDS form wins at any batch size (20 000 dense 64-state systems: 234 ms against 369)
         ka.lds_lu = (P.lds_lu_ok && (P.variant == 2 || (size_t)lanes <= 2u * (size_t)ctx->cus || P.lu_dense)) ? 1u : 0u;
+        // banded factors (bdf_band.h) are a few KB: resident whenever they fit the kernels' LDS budget, whatever the batch size
+        if (P.band_lds) ka.lds_lu = 1u;
         if (c == 0) {
             ka.perm_in = nullptr;
             ka.count_in = nullptr;
@@ -711,8 +713,11 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
         BIND(njev, out->njev, sc_njev, sizeof(uint64_t) * B);
         BIND(nlu, out->nlu, sc_nlu, sizeof(uint64_t) * B);
         HIP_TRY(ctx, ctx->bdf_d.reserve(sizeof(double) * 8 * n * B));
-        HIP_TRY(ctx, ctx->bdf_jac.reserve(sizeof(double) * n * n * B));
-        HIP_TRY(ctx, ctx->bdf_lu.reserve(sizeof(double) * n * n * B));
+        // J and the factors of (I - cJ): one contiguous block per trajectory, n x n or -- a banded hiprtc problem -- by bands
+        uint64_t jac_doubles = (uint64_t)n * (uint64_t)n, lu_doubles = jac_doubles;
+        if (prob->rhs_id == IVP_RHS_JIT) (void)ivp_rhs_jac_layout(prob->jit, nullptr, nullptr, nullptr, &jac_doubles, &lu_doubles);
+        HIP_TRY(ctx, ctx->bdf_jac.reserve(sizeof(double) * jac_doubles * B));
+        HIP_TRY(ctx, ctx->bdf_lu.reserve(sizeof(double) * lu_doubles * B));
         HIP_TRY(ctx, ctx->bdf_piv.reserve(sizeof(uint32_t) * B * (group ? (size_t)n : 1)));   // large n: [B][n] pivot rows
         a.bdf_d = (double *)ctx->bdf_d.p;
         a.bdf_jac = (double *)ctx->bdf_jac.p;
@@ -928,6 +933,10 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
     P.jit = prob->rhs_id == IVP_RHS_JIT;
     P.has_settings = opt->has_settings != 0;
     P.lds_lu_ok = lds_lu_ok;
+    // banded hiprtc problems: no density probe (lds_lu_ok stays false); variant 1 keeps the factors in global memory
+    bool band_fits = false;
+    P.band_lds = group && opt->method == IVP_BDF && prob->rhs_id == IVP_RHS_JIT && ivp_jit_band(prob->jit, nullptr, nullptr, &band_fits) &&
+                 band_fits && opt->variant != 1 && tune().lds_lu != 0;
     P.lu_dense = false;
     P.lu_probed = false;
     P.has_events = n_events > 0;

@@ -15,6 +15,13 @@
 // which BdfG::fd_jac_sparse (bdf_group.h) reads.  Size: 2 n (n_groups + 1) bytes of constant data per code object --
 // 3 KB for a tridiagonal system at n = 512, 512 KB in the worst case (n = 512, every column its own group).  The
 // on-disk cache keys on the generated source, so two patterns never share an entry.
+//
+// Banded storage (IVP_RHS_BANDED, ivp_rhs_compile_sparse only): the bandwidths ml = max(row - col), mu = max(col - row) of
+// the declared pattern travel the same way, as `enum { SP_ML, SP_MU }` in the functor, and bdf_band.h is spliced in
+// behind bdf_group.h.  J and the factors of (I - cJ) are then stored by bands (ivp_rhs_jac_layout), and the BDF chunk
+// kernel exists in two residencies -- factors in LDS for the whole launch, or in global memory -- chosen per launch by
+// the host (IvpKArgs.lds_lu) and kept as separate modules.  A problem without the flag generates the functor text it
+// always did.
 #include "ivp_jit.h"
 
 #include <hip/hiprtc.h>
@@ -51,11 +58,13 @@ struct JitRhs {
     std::string ode_source;
     std::string sparsity_source;   // the pattern's tables as device code (empty: no pattern, or the snippet has its own jac_col)
     int n_groups = 0;
+    bool banded = false;   // IVP_RHS_BANDED: J and the factors by bands (bdf_band.h)
+    int band_ml = 0, band_mu = 0;
     std::string arch;
     std::mutex mu;
     // (device, method, fp_mode, full, ctl): hipModuleLoadData binds a module to the device that is current when it is
     // loaded, so a handle shared by contexts on several GPUs keeps one module per device
-    std::map<std::tuple<int, int, int, int, bool, bool>, JitModule> modules;   // ... , lane-cooperative module
+    std::map<std::tuple<int, int, int, int, bool, bool, bool>, JitModule> modules;   // ... , lane-cooperative module, banded factors in LDS
     std::string log;
 };
 
@@ -115,7 +124,29 @@ std::string sparsity_tables(int n, const std::vector<int32_t> &groups, int n_gro
     return s;
 }
 
-std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, bool coop_only)
+// LDS a banded BDF chunk kernel allocates when its factors are resident (BdfBand::lds_bytes() in bdf_band.h is the same
+// formula, and the kernel asserts it): per trajectory of the wavefront the factors, the pivots, the KJ + 1 = 9 state
+// copies of fd_jac_sparse, the group vector and, with event functions, the event stage.
+constexpr int kBandLdsBudget = 65536;   // IVP_BAND_LDS_BUDGET
+bool band_lds_fits(int n, int ml, int mu, int ne)
+{
+    const long ngroup = IVP_WAVE / ivp_group_width(n);
+    const long w = 2L * ml + mu + 1;
+    return ngroup * n * (8 * (w + 9 + 1 + (ne > 0 ? 1 : 0)) + 4) <= kBandLdsBudget;
+}
+
+// bandwidths of a validated pattern
+void pattern_bandwidth(int n, const int32_t *col_ptr, const int32_t *row_idx, int *ml, int *mu)
+{
+    *ml = 0; *mu = 0;
+    for (int c = 0; c < n; ++c)
+        for (int32_t e = col_ptr[c]; e < col_ptr[c + 1]; ++e) {
+            if (row_idx[e] - c > *ml) *ml = row_idx[e] - c;
+            if (c - row_idx[e] > *mu) *mu = c - row_idx[e];
+        }
+}
+
+std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, bool coop_only, bool band_lds = false)
 {
     // kernel flavour (rk_launch.h): 2 = log-only exists for the adaptive explicit methods of problems without event functions
     const int flavour = (full_in == 2 && r.ne == 0 && (method == IVP_RK23 || method == IVP_DOPRI5 || method == IVP_DOP853)) ? 2 : (full_in ? 1 : 0);
@@ -147,7 +178,11 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
             sp = "  enum { SP_NGROUPS = " + std::to_string(r.n_groups) + " };\n"
                  "  static __device__ __forceinline__ int sp_group_of(int c) { return ivp_sp_group_of[c]; }\n"
                  "  static __device__ __forceinline__ int sp_hit(int e) { return ivp_sp_hit[e]; }\n";
+            if (r.banded) sp += "  enum { SP_ML = " + std::to_string(r.band_ml) + ", SP_MU = " + std::to_string(r.band_mu) + " };\n";
         }
+        const bool band = sparse && r.banded;
+        if (band) s += join(k_src_bdf_band_h);
+        const std::string lds_arg = (band && band_lds) ? ", true" : "";
         std::snprintf(buf, sizeof buf,
                       "namespace ivp_jit { struct RhsUser { enum { N = %d, P = %d, NE = IVP_USER_NE };\n"
                       "  static __device__ __forceinline__ double ode_comp(int i, double x, const double* y, const double* p) { return ::ode_comp(i, x, y, p); }\n"
@@ -160,8 +195,8 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                       "%s"
                       "}; }\n"
                       "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<%d, ivp_jit::RhsUser, %s, %d>(a); }\n"
-                      "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<%d, ivp_jit::RhsUser, %s, %d>(a); }\n",
-                      r.n, r.np, sp.c_str(), method, full, ivp_group_width(r.n), method, full, ivp_group_width(r.n));
+                      "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<%d, ivp_jit::RhsUser, %s, %d%s>(a); }\n",
+                      r.n, r.np, sp.c_str(), method, full, ivp_group_width(r.n), method, full, ivp_group_width(r.n), lds_arg.c_str());
         s += buf;
         return s;
     }
@@ -237,9 +272,9 @@ int load_module(JitRhs &r, const std::vector<char> &code, JitModule *out, bool c
     return IVP_OK;
 }
 
-int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitModule *out, bool coop_only = false)
+int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitModule *out, bool coop_only = false, bool band_lds = false)
 {
-    const std::string src = build_source(r, method, full, ctl, coop_only);
+    const std::string src = build_source(r, method, full, ctl, coop_only, band_lds);
     const std::string opt_key = r.arch + (fp_mode == IVP_FP_FAST ? "|fast" : "|strict");
     const std::string cpath = cache_path(src, opt_key);
     if (!cpath.empty()) {
@@ -298,7 +333,13 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
                     const int32_t *col_ptr, const int32_t *row_idx)
 {
     std::string sparsity_source;
-    int n_groups = 0;
+    int n_groups = 0, ml = 0, mu = 0;
+    const bool banded = (flags & IVP_RHS_BANDED) != 0;
+    if (banded && !col_ptr) { if (log) *log = "IVP_RHS_BANDED needs a jac_sparsity pattern"; return IVP_ERR_BAD_ARGUMENT; }
+    if (banded && (flags & IVP_RHS_HAS_JAC)) {
+        if (log) *log = "IVP_RHS_BANDED with IVP_RHS_HAS_JAC: an analytic jac_col in band storage is not supported";
+        return IVP_ERR_BAD_ARGUMENT;
+    }
     if (col_ptr) {
         std::vector<int32_t> groups;
         std::vector<int16_t> hit;
@@ -307,10 +348,20 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
         if (rc != IVP_OK) { if (log) *log = why; return rc; }
         // a snippet with its own jac_col keeps it and the pattern is dropped (ivp_wrapper.rs:245-258)
         if (!(flags & IVP_RHS_HAS_JAC)) sparsity_source = sparsity_tables(n, groups, n_groups, hit);
+        if (banded) {
+            pattern_bandwidth(n, col_ptr, row_idx, &ml, &mu);
+            if (2 * ml + mu + 1 >= n) {
+                if (log) *log = "IVP_RHS_BANDED: the band (ml = " + std::to_string(ml) + ", mu = " + std::to_string(mu) + ") is as wide as the matrix (2 ml + mu + 1 >= n)";
+                return IVP_ERR_BAD_ARGUMENT;
+            }
+        }
     }
     JitRhs *r = new JitRhs();
     r->sparsity_source = sparsity_source;
     r->n_groups = n_groups;
+    r->banded = banded;
+    r->band_ml = ml;
+    r->band_mu = mu;
     r->device = device;
     r->has_jac = (flags & IVP_RHS_HAS_JAC) != 0;
     r->n = n;
@@ -348,6 +399,16 @@ void ivp_jit_free(void *handle)
 
 const char *ivp_jit_last_log(void *handle) { return handle ? ((JitRhs *)handle)->log.c_str() : ""; }
 
+bool ivp_jit_band(void *handle, int *ml, int *mu, bool *lds_fits)
+{
+    JitRhs *r = (JitRhs *)handle;
+    if (!r || !r->banded) return false;
+    if (ml) *ml = r->band_ml;
+    if (mu) *mu = r->band_mu;
+    if (lds_fits) *lds_fits = band_lds_fits(r->n, r->band_ml, r->band_mu, r->ne);
+    return true;
+}
+
 void ivp_jit_dims(void *handle, int *n, int *np)
 {
     JitRhs *r = (JitRhs *)handle;
@@ -367,11 +428,13 @@ hipError_t ivp_jit_launch(void *handle, int what, int method, int fp_mode, int f
         if (coop && !((r->ne == 0 || full) && (method == IVP_DOPRI5 || method == IVP_DOP853) && r->n <= IVP_MAX_N)) return hipErrorInvalidValue;
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-        auto key = std::make_tuple(dev, method, fp_mode, full, coop ? false : ctl, coop);
+        // banded problems: the BDF chunk kernel with LDS-resident factors is a module of its own (init kernels are the same in both)
+        const bool band_lds = r->banded && method == IVP_BDF && a.lds_lu != 0 && band_lds_fits(r->n, r->band_ml, r->band_mu, r->ne);
+        auto key = std::make_tuple(dev, method, fp_mode, full, coop ? false : ctl, coop, band_lds);
         auto it = r->modules.find(key);
         if (it == r->modules.end()) {
             JitModule nm;
-            if (compile_module(*r, method, fp_mode, full, coop ? false : ctl, &nm, coop) != IVP_OK) return hipErrorInvalidValue;   // r->log says why (ivp_jit_last_log)
+            if (compile_module(*r, method, fp_mode, full, coop ? false : ctl, &nm, coop, band_lds) != IVP_OK) return hipErrorInvalidValue;   // r->log says why (ivp_jit_last_log)
             it = r->modules.emplace(key, nm).first;
         }
         m = it->second;
@@ -415,6 +478,33 @@ int ivp_jac_sparsity_groups(int32_t n, const int32_t *col_ptr, const int32_t *ro
     return IVP_OK;
 }
 
+int ivp_jac_sparsity_bandwidth(int32_t n, const int32_t *col_ptr, const int32_t *row_idx, int32_t *ml_out, int32_t *mu_out)
+{
+    if (!ml_out || !mu_out) return IVP_ERR_BAD_ARGUMENT;
+    std::vector<int32_t> groups;
+    int n_groups = 0;
+    const int rc = group_columns(n, col_ptr, row_idx, groups, &n_groups, nullptr, nullptr);   // the validation of ivp_jac_sparsity_groups
+    if (rc != IVP_OK) return rc;
+    int ml = 0, mu = 0;
+    pattern_bandwidth(n, col_ptr, row_idx, &ml, &mu);
+    *ml_out = ml;
+    *mu_out = mu;
+    return IVP_OK;
+}
+
+int ivp_rhs_jac_layout(const void *handle, int32_t *banded, int32_t *ml, int32_t *mu, uint64_t *jac_doubles, uint64_t *lu_doubles)
+{
+    if (!handle) return IVP_ERR_BAD_ARGUMENT;
+    const JitRhs *r = (const JitRhs *)handle;
+    const uint64_t n = (uint64_t)r->n;
+    if (banded) *banded = r->banded ? 1 : 0;
+    if (ml) *ml = r->banded ? r->band_ml : 0;
+    if (mu) *mu = r->banded ? r->band_mu : 0;
+    if (jac_doubles) *jac_doubles = r->banded ? (uint64_t)(r->band_ml + r->band_mu + 1) * n : n * n;
+    if (lu_doubles) *lu_doubles = r->banded ? (uint64_t)(2 * r->band_ml + r->band_mu + 1) * n : n * n;
+    return IVP_OK;
+}
+
 int ivp_rhs_compile_sparse(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags,
                            const int32_t *col_ptr, const int32_t *row_idx, void **handle)
 {
@@ -422,7 +512,8 @@ int ivp_rhs_compile_sparse(ivp_ctx_t *ctx, const char *source, int32_t n, int32_
     if (!ctx || !source || !handle) return IVP_ERR_BAD_ARGUMENT;
     if (n < 1 || n > IVP_MAX_GROUP_N || n_params < 0 || n_params > IVP_MAX_P || n_events < 0 || n_events > 64)
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
-    if (flags & ~IVP_RHS_HAS_JAC) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if (flags & ~(IVP_RHS_HAS_JAC | IVP_RHS_BANDED)) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if ((flags & IVP_RHS_BANDED) && n <= IVP_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_BANDED needs 8 < n <= 512");
     if (!col_ptr) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "jac_sparsity: col_ptr is NULL");
     std::string log;
     const int rc = ivp_jit_compile(ctx->device, source, n, n_params, n_events, flags, handle, &log, col_ptr, row_idx);

@@ -9,6 +9,9 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
                     const int32_t *col_ptr = nullptr, const int32_t *row_idx = nullptr);
 int ivp_jit_n_events(void *handle);
 void ivp_jit_free(void *handle);
+// banded storage (IVP_RHS_BANDED): true and the bandwidths for a banded problem; lds_fits: the factors of a trajectory fit
+// the LDS budget of the banded kernels (bdf_band.h)
+bool ivp_jit_band(void *handle, int *ml, int *mu, bool *lds_fits);
 void ivp_jit_dims(void *handle, int *n, int *n_params);
 const char *ivp_jit_last_log(void *handle);   // hiprtc build log / load error of the most recent failure
 hipError_t ivp_jit_launch(void *handle, int what, int method, int fp_mode, int full, const IvpKArgs &a,

@@ -28,6 +28,10 @@ sparse matrix, a dense array-like or a ``(col_ptr, row_idx)`` pair; the forward-
 right-hand side per column GROUP (solve.rs:152-210, sparsity.rs).  A pattern that covers every structural non-zero gives
 exactly the results of the solve without it.  A given ``jac`` wins; explicit methods accept and ignore it; for n <= 8
 (thread-per-trajectory kernels, at most 8 columns to save) it raises ``NotImplementedError``.
+``jac_storage="banded"`` (with a pattern, ``method="BDF"``): J and the factors of (I - cJ) are stored by bands with the
+pattern's bandwidths and factorised by the banded kernels -- same results, far less memory and time for method-of-lines
+systems.  Ignored, like the pattern, by explicit methods and when a ``jac`` is given; any value other than ``"full"`` /
+``"banded"`` is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -145,7 +149,7 @@ def _event_config(ev) -> api.EventConfig:
     return cfg
 
 
-def _device_problem(fun: str, n: int, args, events: list, jac, ctx, jac_sparsity=None) -> api.DeviceIVP:
+def _device_problem(fun: str, n: int, args, events: list, jac, ctx, jac_sparsity=None, jac_storage="full") -> api.DeviceIVP:
     if "__device__" in fun:
         src = fun
     elif n <= api.MAX_LANE_N:
@@ -196,16 +200,22 @@ def _device_problem(fun: str, n: int, args, events: list, jac, ctx, jac_sparsity
                     "__device__ void jac_col(int ivp_c, double x, const double* y, double* column, const double* p) {\n"
                     f"  for (int r = 0; r < {n}; ++r) column[r] = 0.0;\n  ivp_jac_proxy j{{column, ivp_c, 0.0}};\n" + jbody + "\n}\n")
     params = () if args is None else tuple(float(a) for a in (args if isinstance(args, (tuple, list)) else (args,)))
-    extra = {} if (has_jac or jac_sparsity is None) else {"jac_sparsity": jac_sparsity}   # a given jac wins (ivp_wrapper.rs:245-258)
+    # a given jac wins (ivp_wrapper.rs:245-258), over the pattern and over the storage that goes with it
+    extra = {} if (has_jac or jac_sparsity is None) else {"jac_sparsity": jac_sparsity, "jac_storage": jac_storage}
     return api.DeviceIVP(src, n, params, ctx=ctx, events=[_event_config(e) for e in events], jac=has_jac, **extra)
 
 
 def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, dense_output: bool = False, events=None,
-              vectorized: bool = False, args=None, jac=None, jac_sparsity=None, ctx: api.Context = None,
+              vectorized: bool = False, args=None, jac=None, jac_sparsity=None, jac_storage: str = "full", ctx: api.Context = None,
               **options) -> OdeResult:
     """``ivp.solve_ivp`` (src/python/solve.rs:150-222).  Recognised ``options``: rtol, atol (scalar or per-component),
     max_step, min_step, first_step, max_steps (solve.rs:292-340); like the reference, other keys are ignored."""
     del vectorized   # accepted and unused, as in the reference (solve.rs:166)
+    if jac_storage not in ("full", "banded"):
+        raise ValueError(f'jac_storage must be "full" or "banded", got {jac_storage!r}')
+    if (jac_storage == "banded" and jac_sparsity is None and jac is None and isinstance(method, str)
+            and api.Method.from_str(method) == api.Method.BDF):
+        raise ValueError('jac_storage="banded" needs a jac_sparsity pattern: the bandwidths are taken from it')
     t0, tf = (float(v) for v in t_span)
     y0v = np.atleast_1d(np.asarray(y0, dtype=np.float64))
     if jac_sparsity is not None and (y0v.size <= api.MAX_LANE_N or not isinstance(fun, str)):
@@ -231,7 +241,8 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
             uses_jac = isinstance(method, str) and api.Method.from_str(method) == api.Method.BDF
             try:
                 # ... and so never read the sparsity pattern either
-                problem = _device_problem(fun, y0v.size, args, ev, jac if uses_jac else None, ctx, jac_sparsity if uses_jac else None)
+                problem = _device_problem(fun, y0v.size, args, ev, jac if uses_jac else None, ctx, jac_sparsity if uses_jac else None,
+                                           jac_storage if uses_jac else "full")
             except api.IvpError as e:   # a snippet that does not compile surfaces like any other solver failure (solve.rs:216-221)
                 raise RuntimeError(f"Solver failed: {e}") from e
         has_events = events is not None

@@ -38,6 +38,7 @@ pub const IVP_ERR_LOG_CAPACITY: c_int = -105;
 
 pub const IVP_RHS_JIT: i32 = 1000;
 pub const IVP_RHS_HAS_JAC: u32 = 1;
+pub const IVP_RHS_BANDED: u32 = 2;
 
 #[repr(C)]
 pub struct ivp_problem_t {
@@ -292,4 +293,9 @@ extern "C" {
     pub fn ivp_jac_sparsity_groups(n: i32, col_ptr: *const i32, row_idx: *const i32, groups_out: *mut i32, n_groups_out: *mut i32) -> c_int;
     pub fn ivp_rhs_compile_sparse(ctx: *mut ivp_ctx_t, source: *const c_char, n: i32, n_params: i32, n_events: i32, flags: u32,
                                   col_ptr: *const i32, row_idx: *const i32, handle: *mut *mut c_void) -> c_int;
+    // `jac_storage = Banded{ml, mu}` (IVP_RHS_BANDED): the bandwidths of a pattern (pure host) and the per-trajectory
+    // Jacobian / factor storage of a compiled problem
+    pub fn ivp_jac_sparsity_bandwidth(n: i32, col_ptr: *const i32, row_idx: *const i32, ml_out: *mut i32, mu_out: *mut i32) -> c_int;
+    pub fn ivp_rhs_jac_layout(handle: *const c_void, banded: *mut i32, ml: *mut i32, mu: *mut i32, jac_doubles: *mut u64,
+                              lu_doubles: *mut u64) -> c_int;
 }
