@@ -33,8 +33,9 @@ extern "C" {
 #define IVP_HIP_ABI_VERSION 5
 
 /* Method: same order as `enum Method`, src/solve/options.rs:14-27. The explicit RK methods (RK23, DOPRI5,
- * DOP853, the fixed-step RK4) and the variable-order implicit BDF are on the accelerated path; RADAU returns
- * IVP_ERR_UNSUPPORTED_METHOD. */
+ * DOP853, the fixed-step RK4) and the variable-order implicit BDF are on the accelerated path of solve_ivp().  RADAU
+ * runs on the device through its direct per-method call, ivp_radau_solve*() below (n <= 8); as ivp_options_t.method
+ * it still returns IVP_ERR_UNSUPPORTED_METHOD from the solve_ivp() entry points. */
 typedef enum {
     IVP_RK23 = 0,
     IVP_DOPRI5 = 1, /* "RK45" */
@@ -65,7 +66,7 @@ typedef enum {
     IVP_ERR_INVALID_STEP_SIZE = -5,       /* ConfigError::InvalidStepSize (RK4: first_step zero / wrong sign, rk4.rs:81-87) */
     IVP_ERR_INVALID_SCALE_FACTORS = -6,   /* ConfigError::InvalidScaleFactors  */
     IVP_ERR_BAD_ARGUMENT = -100,          /* NULL pointer, unknown rhs id, n mismatch ...            */
-    IVP_ERR_UNSUPPORTED_METHOD = -101,    /* RADAU: not on the accelerated path (every other method is, for every n) */
+    IVP_ERR_UNSUPPORTED_METHOD = -101,    /* RADAU as ivp_options_t.method: solve_ivp() does not route to it yet (ivp_radau_solve*() is the way in) */
     IVP_ERR_NO_DEVICE = -102,             /* no HIP device: there is deliberately no CPU fallback    */
     IVP_ERR_HIP = -103,                   /* a HIP runtime call failed; see ivp_last_error_string()  */
     IVP_ERR_JIT = -104,                   /* hiprtc compilation of a user RHS failed                 */
@@ -333,6 +334,47 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
                             void *hip_stream);
 int ivp_batch_poll(ivp_ctx_t *ctx, int *done);
 int ivp_batch_wait(ivp_ctx_t *ctx);
+
+/*
+ * Radau IIA(5), the direct per-method call: B independent RADAU::builder()...build().solve(f, x0, y0, xend, rtol, atol,
+ * Some(&mut DefaultSolOut)) calls (src/methods/radau.rs:19-127) for pure ODEs with the identity mass matrix, n <= 8,
+ * strict arithmetic.  ivp_radau_settings_t carries the struct fields solve_ivp() cannot reach; the fields it can come
+ * from ivp_options_t: rtol / atol (scalar or vector), max_steps (0 = unlimited, the solve_ivp convention), t_eval with
+ * or without t_eval_offsets, first_step, max_step, min_step, dense_output, max_log, chunk_attempts, profile.
+ * opt->method is ignored.  Arguments otherwise as for ivp_batch_solve_device / ivp_batch_solve; settings == NULL means
+ * ivp_radau_settings_default().  out->njev / out->nlu are filled.  dense_output segments are 4 n coefficients
+ * [coef][component]; ivp_dense_eval_device(method = IVP_RADAU) evaluates them.
+ * Errors, reported before the device is touched: the ConfigErrors of radau.rs:132-262 (MUST_BE_POSITIVE: newton_maxiter;
+ * OUT_OF_RANGE: uround, safety_factor, newton_maxiter > 15; INVALID_SCALE_FACTORS; INVALID_STEP_SIZE: first_step == 0;
+ * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 8, problems
+ * with event functions, fp_mode = FMA and variant = 3.  Mass matrices, DAE index sets, banded storage and the CSR
+ * one-pass / dense / events / multi-device forms are not on this path yet.
+ */
+typedef struct {
+    double uround;          /* 2.3e-16 */
+    double safety_factor;   /* 0.9 */
+    double scale_min;       /* 0.2 */
+    double scale_max;       /* 8.0 */
+    double newton_tol;      /* read when has_newton_tol != 0; else derived from the tolerances (radau.rs:198-205) */
+    int32_t newton_maxiter; /* 7; at most 15 */
+    int32_t has_newton_tol; /* 0 */
+    int32_t predictive;     /* 1: Gustafsson controller */
+    int32_t reserved;       /* 0 */
+} ivp_radau_settings_t;
+
+void ivp_radau_settings_default(ivp_radau_settings_t *settings);
+/* The validation of ivp_batch_solve*() (ivp_options_check) and of ivp_radau_solve*() (ivp_radau_check) on its own: no
+ * context, no device.  Returns what the solve would return for these arguments before it touches the device; the text
+ * ivp_last_error_string() would carry goes to message[message_len] (may be NULL). */
+int ivp_options_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, char *message, size_t message_len);
+int ivp_radau_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                    char *message, size_t message_len);
+int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                    const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                    const ivp_radau_settings_t *settings, ivp_batch_result_t *out);
+int ivp_radau_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, ivp_batch_result_t *out, void *hip_stream);
 
 /*
  * Solution.t / Solution.y of B solve_ivp() calls in ONE call and ONE integration (ABI v5).

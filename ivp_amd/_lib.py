@@ -89,6 +89,15 @@ class RunStatsT(C.Structure):
     ]
 
 
+class RadauSettingsT(C.Structure):
+    """``ivp_radau_settings_t``: the RADAU struct's fields solve_ivp() cannot reach (radau.rs:19-66)."""
+    _fields_ = [
+        ("uround", C.c_double), ("safety_factor", C.c_double), ("scale_min", C.c_double), ("scale_max", C.c_double),
+        ("newton_tol", C.c_double), ("newton_maxiter", C.c_int32), ("has_newton_tol", C.c_int32), ("predictive", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/ivp_hip.h declares
 EXPORTS = (
     "ivp_abi_version", "ivp_device_count", "ivp_ctx_create", "ivp_ctx_destroy", "ivp_last_error_string",
@@ -99,6 +108,7 @@ EXPORTS = (
     "ivp_batch_solve_logged", "ivp_batch_solve_logged_device", "ivp_step_log_fetch_device", "ivp_step_log_free", "ivp_batch_solve_logged_multi", "ivp_step_log_fetch_multi",
     "ivp_batch_solve_dense_device", "ivp_batch_solve_dense", "ivp_dense_log_fetch_device", "ivp_dense_log_free", "ivp_dense_eval_device",
     "ivp_batch_solve_events_device", "ivp_batch_solve_events", "ivp_event_log_fetch_device", "ivp_event_log_free",
+    "ivp_radau_settings_default", "ivp_radau_solve", "ivp_radau_solve_device", "ivp_options_check", "ivp_radau_check",
 )
 
 ERRORS = {
@@ -166,6 +176,16 @@ def load():
     L.ivp_batch_wait.restype = C.c_int
     L.ivp_batch_wait.argtypes = [C.c_void_p]
     L.ivp_batch_solve_multi.restype = C.c_int
+    L.ivp_radau_settings_default.restype = None
+    L.ivp_radau_settings_default.argtypes = [C.POINTER(RadauSettingsT)]
+    L.ivp_options_check.restype = C.c_int
+    L.ivp_options_check.argtypes = [C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT), C.c_char_p, C.c_size_t]
+    L.ivp_radau_check.restype = C.c_int
+    L.ivp_radau_check.argtypes = [C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT), C.POINTER(RadauSettingsT), C.c_char_p, C.c_size_t]
+    L.ivp_radau_solve.restype = C.c_int
+    L.ivp_radau_solve.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1]]
+    L.ivp_radau_solve_device.restype = C.c_int
+    L.ivp_radau_solve_device.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1], C.c_void_p]
     L.ivp_batch_solve_multi.argtypes = [C.POINTER(ShardT), C.c_int32, C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT),
                                         C.c_int32, C.POINTER(BatchResultT)]
     L.ivp_batch_solve_multi_host.restype = C.c_int

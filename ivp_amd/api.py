@@ -627,6 +627,9 @@ def _interpolate(method: Method, xi: float, cont: np.ndarray, n: int, xold: floa
         for k in range(order):
             out = out + blk[:, 1 + k] * p[k]
         return out
+    if method == Method.RADAU:  # radau.rs:798-809
+        s = (xi - (xold + h)) / h
+        return c[0] + s * (c[1] + (s - (-0.3550510257216822)) * (c[2] + (s - (-0.8449489742783178)) * c[3]))
     if method == Method.RK4:  # rk4.rs:229-244
         t = (xi - xold) / h
         t2 = t * t
@@ -891,7 +894,7 @@ class PendingBatch:
 
 
 def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None):
+                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None, _radau=None):
     """B independent ``solve_ivp(f, t0[b], t1[b], y0[:, b], options)`` calls on the GPU.
 
     ``y0``: ``[n, B]`` float64, numpy (host path: staged through the library) or a CUDA torch tensor
@@ -954,13 +957,17 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
     keep: list = []
     copt = options._c(n, keep)
     method = options.method_enum
+    if _radau is not None:   # the direct Radau call (ivp_amd.Radau): Options.method is ignored
+        if not wait or _steplog is not None or _dense is not None or _events is not None:
+            raise ValueError("Radau: the resumable, one-pass log, CSR dense and CSR event forms are not on its path yet")
+        method = Method.RADAU
     per_traj = options.t_eval_per_trajectory is not None
     if per_traj:
         if len(options.t_eval_per_trajectory) != B:
             raise ValueError(f"t_eval_per_trajectory needs one grid per trajectory ({B}), got {len(options.t_eval_per_trajectory)}")
     ne = 0 if options.t_eval is None else len(options.t_eval)
     ml = int(options.max_log)
-    nc = method.coeffs_per_state() * n if method != Method.RADAU else 0
+    nc = method.coeffs_per_state() * n if (method != Method.RADAU or _radau is not None) else 0
 
     res = out or BatchSolution(
         y_end=xp_zeros((n, B), f64), t_end=xp_zeros((B,), f64), status=xp_zeros((B,), i32),
@@ -1096,6 +1103,14 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
                                                    ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_steplog), stream)
         if rc == -105:   # IVP_ERR_LOG_CAPACITY: the integration is complete, the records wait in the pool for larger buffers
             rc = 0
+    elif _radau is not None and on_device:
+        import torch
+        stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
+        rc = ctx.lib.ivp_radau_solve_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                            ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(r), stream)
+    elif _radau is not None:
+        rc = ctx.lib.ivp_radau_solve(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                     ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(r))
     elif on_device:
         import torch
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
@@ -1371,11 +1386,11 @@ def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = N
 
 
 def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Options = None,
-              ctx: Context = None) -> Solution:
+              ctx: Context = None, _radau=None) -> Solution:
     """``solve_ivp(&f, x0, xend, &y0, options) -> Result<Solution, Error>`` (solve_ivp.rs:99-108) for
     one trajectory, executed by the GPU kernels (a batch of one).  ``Err(..)`` becomes an exception."""
     options = options or Options()
-    method = options.method_enum
+    method = options.method_enum if _radau is None else Method.RADAU   # ivp_amd.Radau.solve: the direct per-method call
     y0 = np.asarray(y0, dtype=np.float64)
     n = y0.size
     n_events = f.n_events()
@@ -1406,7 +1421,7 @@ def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Opti
         pr = np.asarray(f.params(), dtype=np.float64).reshape(f.n_params, 1) if f.n_params else None
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx)
+            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx, _radau=_radau)
         used = 0
         if r.n_log is not None:
             used = max(used, int(r.n_log[0]))

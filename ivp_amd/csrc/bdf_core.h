@@ -872,17 +872,25 @@ IVP_HD uint32_t bdf_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_ou
     return it;
 }
 
+// Radau IIA(5): radau_core.h, included after this file by the translation units that instantiate M_RADAU
+template <class R, int FULL>
+IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j);
+template <class R, int FULL>
+IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out);
+
 // method dispatch used by the kernels (rk_global.h) and the CPU emulation harness
 template <int M, class R, int FULL>
 IVP_HD int32_t any_init_body(const IvpKArgs &a, uint32_t j)
 {
     if constexpr (M == M_BDF) return bdf_init_body<R, FULL>(a, j);
+    else if constexpr (M == M_RADAU) return radau_init_body<R, FULL>(a, j);
     else return init_body<M, R, FULL>(a, j);
 }
 template <int M, class R, int FULL, bool CTL = false>
 IVP_HD uint32_t any_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out)
 {
     if constexpr (M == M_BDF) return bdf_chunk_body<R, FULL>(a, j, status_out);
+    else if constexpr (M == M_RADAU) return radau_chunk_body<R, FULL>(a, j, status_out);
     else return chunk_body<M, R, FULL, CTL>(a, j, status_out);
 }
 

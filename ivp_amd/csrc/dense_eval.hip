@@ -239,6 +239,7 @@ hipError_t IVP_DENSE_EVAL_NAME(int method, const DenseEvalArgs &e, hipStream_t s
     case M_DOP853: return launch_eval<M_DOP853>(e, s);
     case M_RK4: return launch_eval<M_RK4>(e, s);
     case M_BDF: return launch_eval<M_BDF>(e, s);
+    case M_RADAU: return launch_eval<M_RADAU>(e, s);
     }
     return hipErrorInvalidValue;
 }

@@ -80,7 +80,7 @@ void set_active(ivp_ctx *ctx, bool on)
 // (dopri5.rs:143-198, dop853.rs:135-193, rk23.rs:102-129) for the fields solve_ivp() can set, plus
 // the Tolerance length rule (mod.rs:156-161).
 }  // namespace
-int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out)
+int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, bool radau)
 {
     if (!prob || !opt) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null problem/options");
     int n, p;
@@ -98,17 +98,17 @@ int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const 
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "problem dims (n=%d,p=%d) do not match rhs (n=%d,p=%d)", prob->n, prob->n_params, n, p);
     if (n < 1 || n > IVP_MAX_GROUP_N || p > IVP_MAX_P) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
     if (B == 0 || B > 0x7FFFFFFFull) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "batch size %zu out of range", B);
-    if (opt->method == IVP_RADAU)
-        return fail(ctx, IVP_ERR_UNSUPPORTED_METHOD, "method %d (RADAU) is not on the accelerated path", opt->method);
+    if (opt->method == IVP_RADAU && !radau)
+        return fail(ctx, IVP_ERR_UNSUPPORTED_METHOD, "method %d (RADAU) is not on the accelerated path of solve_ivp (ivp_radau_solve is the direct call)", opt->method);
     if (opt->method < IVP_RK23 || opt->method > IVP_BDF) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown method %d", opt->method);
-    if (opt->method == IVP_BDF) {   // BDF::solve validates tolerances, bdf.rs:112-128
+    if (opt->method == IVP_BDF || radau) {   // BDF::solve validates tolerances, bdf.rs:112-128
         for (int i = 0; i < n; ++i) {
             const double rt = opt->rtol_vec ? opt->rtol_vec[i < opt->rtol_vec_len ? i : 0] : opt->rtol;
             const double at = opt->atol_vec ? opt->atol_vec[i < opt->atol_vec_len ? i : 0] : opt->atol;
             if (rt < 0.0 || at < 0.0) return fail(ctx, IVP_ERR_NEGATIVE_TOLERANCE, "negative tolerance at component %d", i);
         }
     }
-    if (opt->has_settings) {   // XXX::solve() input validation, in the reference's order
+    if (opt->has_settings && !radau) {   // XXX::solve() input validation, in the reference's order
         const MethodSettings m = settings_of(opt);
         if (opt->method == IVP_DOPRI5 || opt->method == IVP_DOP853) {   // dopri5.rs:143-198, dop853.rs:135-193
             if (m.uround <= 1e-35 || m.uround >= 1.0) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "uround = %g outside (1e-35, 1)", m.uround);
@@ -193,6 +193,7 @@ hipError_t pend_launch(ivp_ctx *ctx, int what, const IvpKArgs &ka, uint32_t lane
     const bool fast = P.fp_mode == IVP_FP_FAST;
     if (P.jit) return ivp_jit_launch(P.prob.jit, (use_coop && what == IVP_LAUNCH_CHUNK) ? IVP_LAUNCH_COOP : what, P.method, P.fp_mode, P.full, ka, lanes, s);
     if (P.group) return (fast ? ivp_launch_group_fast : ivp_launch_group_strict)(what, P.method, P.prob.rhs_id, P.full, ka, lanes, s);
+    if (P.method == IVP_RADAU) return ivp_launch_radau_strict(what, P.prob.rhs_id, P.full, ka, lanes, s);
     if (P.method == IVP_BDF) {
         // more than one full wave per SIMD still running: the two-waves-per-SIMD build (rk_bdf.hip); same bits either way
         const bool occ2 = what == IVP_LAUNCH_CHUNK && (lanes > ctx->one_wave_per_simd() || tune().bdf_occ2 == 1) && tune().bdf_occ2 != 0;
@@ -271,7 +272,7 @@ int enqueue_round(ivp_ctx *ctx)
     // one wave per CU -- down to a single trajectory per wave (256 trajectories: 4.9 ms with one lane per wave, 6.6 with
     // two, 9.6 with eight: the fewer lanes, the fewer phases a wave runs on behalf of some other lane).
     uint32_t lpw = 0;
-    if (P.method == IVP_BDF && !P.group) {   // built-in and hiprtc right-hand sides alike
+    if ((P.method == IVP_BDF || P.method == IVP_RADAU) && !P.group) {   // built-in and hiprtc right-hand sides alike; Radau starts from BDF's policy
         const uint32_t cus = ctx->cus;
         const uint32_t want = tune().bdf_lpw > 0 ? (uint32_t)tune().bdf_lpw : std::max(1u, (lanes + cus - 1u) / cus);
         lpw = std::min(64u, want);
@@ -291,7 +292,7 @@ int enqueue_round(ivp_ctx *ctx)
     // (and only while this solve has the device to itself: with other solves in flight the SIMDs a ragged round leaves idle
     // are not idle)
     const bool alone = inflight_on(ctx->device).load(std::memory_order_relaxed) <= 1;
-    if (tune().window && alone && P.adaptive && !P.group && !use_coop && !tail && lpw == 0 && P.method != IVP_BDF && !P.has_events &&
+    if (tune().window && alone && P.adaptive && !P.group && !use_coop && !tail && lpw == 0 && P.method != IVP_BDF && P.method != IVP_RADAU && !P.has_events &&
         (P.n >= 4 || tune().window == 2)) {
         const uint32_t full = lanes / kOneWavePerSimd;
         if (full >= 1 && full < 4 && (uint64_t)lanes * 5u < (uint64_t)(full + 1u) * kOneWavePerSimd * 4u) window = full * kOneWavePerSimd;
@@ -532,7 +533,7 @@ void ivp_ctx_destroy(ivp_ctx_t *c)
     DevBuf *bufs[] = {&c->k1, &c->facold, &c->hlamb, &c->flags, &c->perm[0], &c->perm[1], &c->counts, &c->slot, &c->ran, &c->teval, &c->teval_off, &c->evcfg, &c->tolvec, &c->zero_off,
                       &c->sc_y, &c->sc_x, &c->sc_h, &c->sc_status, &c->sc_nfev, &c->sc_nstep, &c->sc_naccpt, &c->sc_nrejct,
                       &c->sc_next_idx, &c->sc_n_filled, &c->sc_n_log, &c->sc_n_seg, &c->sc_t_last,
-                      &c->bdf_d, &c->bdf_jac, &c->bdf_lu, &c->bdf_piv, &c->sc_njev, &c->sc_nlu, &c->prev_event, &c->sc_n_ev,
+                      &c->bdf_d, &c->bdf_jac, &c->bdf_lu, &c->bdf_piv, &c->rad_mat, &c->rad_cont, &c->rad_piv, &c->sc_njev, &c->sc_nlu, &c->prev_event, &c->sc_n_ev,
                       &c->st_y0, &c->st_params, &c->st_t0, &c->st_t1, &c->st_logoff,
                       &c->log_pool, &c->log_alloc, &c->def_rec, &c->evd_rec, &c->evd_cnt, &c->log_off, &c->log_bsum, &c->st_log_t, &c->st_log_y};
     for (DevBuf *b : bufs) b->release();
@@ -597,15 +598,48 @@ int ivp_rhs_n_events(int32_t rhs_id)
     return kRhsEvents[rhs_id];
 }
 
-int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
-                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
-                            ivp_batch_result_t *out, void *hip_stream)
+}  // extern "C"
+
+namespace {
+
+// RADAU::solve's input validation (radau.rs:132-262) for the fields of ivp_radau_settings_t / ivp_options_t, after the
+// checks every entry point shares; what the Radau path does not cover yet is IVP_ERR_BAD_ARGUMENT.  No device is touched.
+int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *rad, int *n_out, int *p_out)
+{
+    const int rc = validate(ctx, prob, B, opt, n_out, p_out, true);
+    if (rc != IVP_OK) return rc;
+    const int n = *n_out;
+    if (n > IVP_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_MAX_N);
+    const int n_events = prob->rhs_id == IVP_RHS_JIT ? ivp_jit_n_events(prob->jit) : kRhsEvents[prob->rhs_id];
+    if (n_events > 0) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for problems with event functions: not yet on the accelerated path");
+    if (opt->fp_mode != IVP_FP_STRICT) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with fp_mode = FMA: not yet (strict arithmetic only)");
+    if (opt->variant == 3) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with variant = 3 (lane-cooperative kernels): not yet");
+    if (rad->uround <= 1e-35 || rad->uround >= 1.0) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "uround = %g outside (1e-35, 1)", rad->uround);
+    if (rad->safety_factor <= 1e-4 || rad->safety_factor >= 1.0) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "safety_factor = %g outside (1e-4, 1)", rad->safety_factor);
+    if (rad->scale_min <= 0.0 || !(rad->scale_min < rad->scale_max))
+        return fail(ctx, IVP_ERR_INVALID_SCALE_FACTORS, "scale factors min = %g, max = %g", rad->scale_min, rad->scale_max);
+    if (rad->newton_maxiter <= 0) return fail(ctx, IVP_ERR_MUST_BE_POSITIVE, "newton_maxiter must be positive");
+    if (rad->newton_maxiter > 15) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "newton_maxiter = %d outside [1, 15] (the device's Newton loop is bounded)", rad->newton_maxiter);
+    if (opt->has_first_step && opt->first_step == 0.0) return fail(ctx, IVP_ERR_INVALID_STEP_SIZE, "Radau: first_step is zero");
+    return IVP_OK;
+}
+
+int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                ivp_batch_result_t *out, void *hip_stream, const ivp_radau_settings_t *rad)
 {
     if (!ctx) return IVP_ERR_BAD_ARGUMENT;
     if (ctx->pend.active) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "a solve is already in flight on this context");
     ctx->err.clear();
     int n = 0, np = 0;
-    int rc = validate(ctx, prob, B, opt, &n, &np);
+    ivp_options_t radau_opt;
+    if (rad && opt) {   // the direct call: opt->method is ignored, the controller fields are the Radau struct's
+        radau_opt = *opt;
+        radau_opt.method = IVP_RADAU;
+        radau_opt.has_settings = 0;
+        opt = &radau_opt;
+    }
+    int rc = rad ? radau_validate(ctx, prob, B, opt, rad, &n, &np) : validate(ctx, prob, B, opt, &n, &np);
     if (rc != IVP_OK) return rc;
     if (!y0 || !t0 || !t1 || !out) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null y0/t0/t1/out");
     if (np > 0 && !params) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "params required (n_params=%d)", np);
@@ -691,6 +725,15 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
         a.ctl_nstiff = m.nstiff;
         a.has_ctl = opt->has_settings ? 1 : 0;
     }
+    if (rad) {   // the RADAU struct's fields (radau.rs:19-66) where radau_core.h reads them
+        a.ctl_uround = rad->uround;
+        a.ctl_safety = rad->safety_factor;
+        a.ctl_facc1 = 1.0 / rad->scale_min;   // facl, radau.rs:165
+        a.ctl_facc2 = 1.0 / rad->scale_max;   // facr
+        a.ctl_beta = rad->newton_tol;
+        a.ctl_nstiff = (uint64_t)rad->newton_maxiter | (rad->has_newton_tol ? 0x100ull : 0ull) | (rad->predictive ? 0x200ull : 0ull);   // IVP_RAD_*
+        a.has_ctl = 0;
+    }
 
     // ---- state / result arrays: the caller's buffers where given, context scratch otherwise ----
 #define BIND(field, userptr, scratch, bytes)                                   \
@@ -709,7 +752,18 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
     BIND(nstep, out->nstep, sc_nstep, sizeof(uint64_t) * B);
     BIND(naccpt, out->naccpt, sc_naccpt, sizeof(uint64_t) * B);
     BIND(nrejct, out->nrejct, sc_nrejct, sizeof(uint64_t) * B);
-    if (opt->method == IVP_BDF) {
+    if (opt->method == IVP_RADAU) {
+        BIND(njev, out->njev, sc_njev, sizeof(uint64_t) * B);
+        BIND(nlu, out->nlu, sc_nlu, sizeof(uint64_t) * B);
+        // Radau's state lives behind the BDF members of the argument block (ivp_kargs.h), in buffers of its own
+        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * 4 * n * n * B));
+        HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (4 * n + 2) * B));
+        HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B));
+        a.bdf_jac = (double *)ctx->rad_mat.p;
+        a.bdf_d = (double *)ctx->rad_cont.p;
+        a.bdf_piv = (uint32_t *)ctx->rad_piv.p;
+        a.bdf_lu = nullptr;
+    } else if (opt->method == IVP_BDF) {
         BIND(njev, out->njev, sc_njev, sizeof(uint64_t) * B);
         BIND(nlu, out->nlu, sc_nlu, sizeof(uint64_t) * B);
         HIP_TRY(ctx, ctx->bdf_d.reserve(sizeof(double) * 8 * n * B));
@@ -978,6 +1032,74 @@ int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
     return rc;
 }
 
+}  // namespace
+
+extern "C" {
+
+int ivp_batch_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                            ivp_batch_result_t *out, void *hip_stream)
+{
+    return submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, nullptr);
+}
+
+void ivp_radau_settings_default(ivp_radau_settings_t *r)
+{   // RADAU::default(), radau.rs:68-90
+    if (!r) return;
+    std::memset(r, 0, sizeof *r);
+    r->uround = 2.3e-16;
+    r->safety_factor = 0.9;
+    r->scale_min = 0.2;
+    r->scale_max = 8.0;
+    r->newton_maxiter = 7;
+    r->has_newton_tol = 0;
+    r->predictive = 1;
+}
+
+static void copy_message(const ivp_ctx &c, char *message, size_t message_len)
+{
+    if (!message || !message_len) return;
+    std::snprintf(message, message_len, "%s", c.err.c_str());
+}
+
+int ivp_options_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, char *message, size_t message_len)
+{
+    ivp_ctx scratch;   // a plain object: carries the message, owns no device memory, touches no HIP call
+    int n = 0, np = 0;
+    const int rc = validate(&scratch, prob, B, opt, &n, &np);
+    copy_message(scratch, message, message_len);
+    return rc;
+}
+
+int ivp_radau_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                    char *message, size_t message_len)
+{
+    ivp_ctx scratch;
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    int n = 0, np = 0, rc;
+    if (!prob || !opt) rc = fail(&scratch, IVP_ERR_BAD_ARGUMENT, "null problem/options");
+    else {
+        ivp_options_t o = *opt;   // the direct call ignores opt->method and the explicit methods' controller fields
+        o.method = IVP_RADAU;
+        o.has_settings = 0;
+        rc = radau_validate(&scratch, prob, B, &o, settings ? settings : &dflt, &n, &np);
+    }
+    copy_message(scratch, message, message_len);
+    return rc;
+}
+
+int ivp_radau_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, ivp_batch_result_t *out, void *hip_stream)
+{
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, settings ? settings : &dflt);
+    if (rc != IVP_OK) return rc;
+    return ivp_batch_wait(ctx);
+}
+
 int ivp_batch_poll(ivp_ctx_t *ctx, int *done)
 {
     if (!ctx || !done) return IVP_ERR_BAD_ARGUMENT;
@@ -1116,12 +1238,8 @@ int drive_all(ivp_ctx_t *const *ctxs, const char *live, int n)
     return rc_first;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ivp_batch_solve_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt,
-                          int32_t gather_device, ivp_batch_result_t *gathered)
+int multi_impl(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt,
+               int32_t gather_device, ivp_batch_result_t *gathered, const ivp_radau_settings_t *rad)
 {
     if (!shards || n_shards <= 0 || n_shards > 64) return IVP_ERR_BAD_ARGUMENT;
     DeviceGuard restore_device;   // hipSetDevice below must not leak into the caller (its allocations / launches follow the current device)
@@ -1167,8 +1285,8 @@ int ivp_batch_solve_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_probl
         ivp_shard_t &sh = shards[i];
         ctxs[i] = sh.ctx;
         if (sh.count == 0) continue;
-        rc = ivp_batch_submit_device(sh.ctx, prob, sh.count, sh.y0, sh.params, sh.t0, sh.t0_len, sh.t1, sh.t1_len, grids ? &shard_opt[i] : opt, &sh.out,
-                                     sh.hip_stream);
+        rc = submit_impl(sh.ctx, prob, sh.count, sh.y0, sh.params, sh.t0, sh.t0_len, sh.t1, sh.t1_len, grids ? &shard_opt[i] : opt, &sh.out,
+                         sh.hip_stream, rad);
         if (rc == IVP_OK) live[i] = 1;
         else if (sh.ctx != c0) c0->err = sh.ctx->err;   // the caller reads the first context's message
     }
@@ -1181,7 +1299,7 @@ int ivp_batch_solve_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_probl
 
     // ---- gather: shard columns into the batch-wide arrays on gather_device ----
     int n = 0, np = 0;
-    rc = validate(c0, prob, B ? B : 1, opt, &n, &np);
+    rc = validate(c0, prob, B ? B : 1, opt, &n, &np, rad != nullptr);
     if (rc != IVP_OK) return rc;
     MemberDesc md[kMembers];
     member_table(result_shape(prob, opt, n), md);
@@ -1247,11 +1365,19 @@ int ivp_batch_solve_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_probl
     return IVP_OK;
 }
 
-int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_problem_t *prob, size_t B, const double *y0,
-                               const double *params, const double *t0, size_t t0_len, const double *t1, size_t t1_len,
-                               const ivp_options_t *opt, ivp_batch_result_t *out)
+// the host-pointer solve: stage in, integrate shard by shard, stage out (rad != NULL: the direct Radau call, one context)
+int multi_host_impl(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_problem_t *prob, size_t B, const double *y0,
+                    const double *params, const double *t0, size_t t0_len, const double *t1, size_t t1_len,
+                    const ivp_options_t *opt, ivp_batch_result_t *out, const ivp_radau_settings_t *rad)
 {
     if (!ctxs || n_ctx <= 0 || n_ctx > 64 || !ctxs[0]) return IVP_ERR_BAD_ARGUMENT;
+    ivp_options_t radau_opt;
+    if (rad && opt) {   // opt->method is ignored by the direct call: the result shapes below are Radau's
+        radau_opt = *opt;
+        radau_opt.method = IVP_RADAU;
+        radau_opt.has_settings = 0;
+        opt = &radau_opt;
+    }
     DeviceGuard restore_device;
     ivp_ctx_t *c0 = ctxs[0];
     for (int i = 0; i < n_ctx; ++i) {
@@ -1260,7 +1386,7 @@ int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_
     }
     c0->err.clear();
     int n = 0, np = 0;
-    int rc = validate(c0, prob, B, opt, &n, &np);
+    int rc = rad ? radau_validate(c0, prob, B, opt, rad, &n, &np) : validate(c0, prob, B, opt, &n, &np);
     if (rc != IVP_OK) return rc;
     if (!y0 || !t0 || !t1 || !out) return fail(c0, IVP_ERR_BAD_ARGUMENT, "null y0/t0/t1/out");
     if (np > 0 && !params) return fail(c0, IVP_ERR_BAD_ARGUMENT, "params required (n_params=%d)", np);
@@ -1354,7 +1480,7 @@ int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_
             S.out.log_offsets = (const uint64_t *)S.ctx->st_logoff.p;
         }
     }
-    rc = ivp_batch_solve_multi(sh.data(), n_ctx, prob, B, opt, 0, nullptr);
+    rc = multi_impl(sh.data(), n_ctx, prob, B, opt, 0, nullptr, rad);
     if (rc != IVP_OK) return rc;
     for (int i = 0; i < n_ctx; ++i) {
         ivp_shard_t &S = sh[i];
@@ -1383,6 +1509,33 @@ int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_
         HIP_TRY(c0, hipStreamSynchronize(nullptr));
     }
     return IVP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivp_batch_solve_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt,
+                          int32_t gather_device, ivp_batch_result_t *gathered)
+{
+    return multi_impl(shards, n_shards, prob, B, opt, gather_device, gathered, nullptr);
+}
+
+int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_problem_t *prob, size_t B, const double *y0,
+                               const double *params, const double *t0, size_t t0_len, const double *t1, size_t t1_len,
+                               const ivp_options_t *opt, ivp_batch_result_t *out)
+{
+    return multi_host_impl(ctxs, n_ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, nullptr);
+}
+
+int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                    const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                    const ivp_radau_settings_t *settings, ivp_batch_result_t *out)
+{
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    ivp_ctx_t *one[1] = {ctx};
+    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, settings ? settings : &dflt);
 }
 
 int ivp_rhs_compile(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_t n_params, void **handle)

@@ -53,6 +53,7 @@ struct ivp_ctx {
     ivp_host::DevBuf sc_y, sc_x, sc_h, sc_status, sc_nfev, sc_nstep, sc_naccpt, sc_nrejct;
     ivp_host::DevBuf sc_next_idx, sc_n_filled, sc_n_log, sc_n_seg, sc_t_last;
     ivp_host::DevBuf bdf_d, bdf_jac, bdf_lu, bdf_piv, sc_njev, sc_nlu, prev_event, sc_n_ev;
+    ivp_host::DevBuf rad_mat, rad_cont, rad_piv;   // Radau IIA(5) state: J / E1 / E2r / E2i, cont + h_acc + err_acc, pivot words (radau_core.h)
     // staging for the host-pointer entry point
     ivp_host::DevBuf st_y0, st_params, st_t0, st_t1;
     ivp_host::DevBuf st_out[24];
@@ -153,7 +154,8 @@ hipError_t copy_rows(void *dst, size_t dst_stride, const void *src, size_t src_s
 hipError_t copy_rows_peer(void *dst, int dst_dev, size_t dst_stride, const void *src, int src_dev, size_t src_stride, size_t elem,
                           size_t count, size_t rows, hipStream_t s);
 // Options / problem validation shared by every entry point (ivp_capi.cpp)
-int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out);
+// (radau: the call comes from ivp_radau_solve*(), the only entry points that integrate with IVP_RADAU)
+int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, bool radau = false);
 // restores the caller's current HIP device when a multi-device entry point returns
 struct DeviceGuard {
     int dev = -1;

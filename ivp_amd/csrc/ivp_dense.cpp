@@ -405,7 +405,6 @@ int ivp_dense_eval_device(ivp_ctx_t *ctx, int32_t method, int32_t n, int32_t fp_
 {
     if (!ctx) return IVP_ERR_BAD_ARGUMENT;
     ctx->err.clear();
-    if (method == IVP_RADAU) return fail(ctx, IVP_ERR_UNSUPPORTED_METHOD, "RADAU is not on the accelerated path");
     if (method < IVP_RK23 || method > IVP_BDF) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "method %d", method);
     if (n < 1 || n > 512) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "n = %d (1 .. 512)", n);
     if (fp_mode != IVP_FP_STRICT && fp_mode != IVP_FP_FMA) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "fp_mode %d", fp_mode);

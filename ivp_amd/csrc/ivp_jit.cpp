@@ -158,7 +158,9 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
     s += "#define IVP_USER_NE " + std::to_string(r.ne) + "\n";
     s += std::string("#define IVP_USER_JAC ") + (r.has_jac ? "1" : "0") + "\n";
     const bool group = r.n > IVP_MAX_N;   // wave-per-trajectory kernels (rk_group.h): user code defines ode_comp()
-    if (group || coop_only) s += "#define IVP_HOIST 2\n";   // a wave that owns its SIMD: coefficients pinned in registers (rk_core.h KC)
+    const bool radau = method == IVP_RADAU;   // radau_core.h: thread per trajectory, n <= 8, built like rk_radau.hip
+    if (group || coop_only || radau) s += "#define IVP_HOIST 2\n";   // a wave that owns its SIMD: coefficients pinned in registers (rk_core.h KC)
+    if (radau) s += "#define IVP_MIN_WAVES 1\n";
     s += join(k_src_ivp_kargs_h);
     s += "\n// ---- user right-hand side ----\n";
     s += r.ode_source;
@@ -201,6 +203,7 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
         return s;
     }
     s += join(k_src_bdf_core_h);
+    if (radau) s += join(k_src_radau_core_h);   // only the Radau modules: every other module's source stays what it was
     s += join(k_src_rk_global_h);
     std::snprintf(buf, sizeof buf,
                   "namespace ivp_jit { struct RhsUser { enum { N = %d, P = %d, NE = IVP_USER_NE };\n"

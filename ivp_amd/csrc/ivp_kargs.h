@@ -102,6 +102,10 @@ struct IvpKArgs {
     double *prev_event;       // [NE][B]
     double *t_term;           // [B] time of the terminal-event sample in t_eval mode (eval_idx = -1)
     // ---- BDF (variable-order implicit) state ----
+    // (Radau IIA(5), radau_core.h, has no fields of its own -- the block's layout is shared with every kernel and with the
+    //  host emulation: it keeps J, E1, E2r, E2i in bdf_jac [4 n n][B], cont + h_acc + err_acc in bdf_d [4 n + 2][B], its two
+    //  pivot words in bdf_piv [2][B], hold in hlamb, faccon in facold, f0 in k1, and reads the RADAU struct's fields from
+    //  ctl_uround / ctl_safety / ctl_facc1 / ctl_facc2 / ctl_beta (newton_tol) / ctl_nstiff (newton_maxiter | flags))
     double min_step;          // Options.min_step
     int32_t has_min_step;
     double *bdf_d;            // [8*N][B]   differences array D (bdf.rs:220)

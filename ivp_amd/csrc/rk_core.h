@@ -879,6 +879,11 @@ IVP_HD void interpolate(double xi, double *yi, const CP &cont, double xold, doub
 #pragma unroll
         for (int i = 0; i < N; ++i)
             yi[i] = IVP_LC(h00, cont[i], h10 * h, cont[N + i], h01, cont[3 * N + i], h11 * h, cont[2 * N + i]);
+    } else if constexpr (M == M_RADAU) {   // radau.rs:798-809: the collocation polynomial, anchored at the step's END (no fused site)
+        const double s = (xi - (xold + h)) / h;
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            yi[i] = cont[i] + s * (cont[N + i] + (s - (-0.3550510257216822)) * (cont[2 * N + i] + (s - (-0.8449489742783178)) * cont[3 * N + i]));
     } else {
         const double xc = (xi - xold) / h;
         const double x2 = xc * xc;

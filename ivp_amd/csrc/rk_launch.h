@@ -37,3 +37,7 @@ hipError_t ivp_launch_bdf_fast(int what, int rhs_id, int full, const IvpKArgs &a
 // ... and the same source under __launch_bounds__(64, 2) for batches that over-subscribe the chip (see rk_bdf.hip)
 hipError_t ivp_launch_bdf_strict_occ2(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t lanes, hipStream_t s);
 hipError_t ivp_launch_bdf_fast_occ2(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t lanes, hipStream_t s);
+
+// thread-per-trajectory Radau IIA(5) kernels (rk_radau.hip: pinned-coefficient build, strict arithmetic, n <= 8,
+// built-in right-hand sides 0-10 and 15)
+hipError_t ivp_launch_radau_strict(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t lanes, hipStream_t s);

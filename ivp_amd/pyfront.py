@@ -238,7 +238,7 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
             problem = _Degenerate(y0v.size, len(ev))
         else:
             # the explicit methods never call the Jacobian (the reference accepts and ignores it there)
-            uses_jac = isinstance(method, str) and api.Method.from_str(method) == api.Method.BDF
+            uses_jac = isinstance(method, str) and api.Method.from_str(method) in (api.Method.BDF, api.Method.RADAU)
             try:
                 # ... and so never read the sparsity pattern either
                 problem = _device_problem(fun, y0v.size, args, ev, jac if uses_jac else None, ctx, jac_sparsity if uses_jac else None,
@@ -257,7 +257,11 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
         max_step=options.get("max_step"), min_step=options.get("min_step"),
         t_eval=None if t_eval is None else np.asarray(t_eval, dtype=np.float64), dense_output=bool(dense_output))
     try:
-        s = api.solve_ivp(problem, t0, tf, y0v, opts, ctx)
+        if opts.method_enum == api.Method.RADAU:   # solve.rs:224-232 "Radau": the direct per-method call (ivp_amd.Radau)
+            from .radau import Radau
+            s = Radau().solve(problem, t0, tf, y0v, opts, ctx)
+        else:
+            s = api.solve_ivp(problem, t0, tf, y0v, opts, ctx)
     except api.IvpError as e:   # solve.rs:216-221
         raise RuntimeError(f"Solver failed: {e}") from e
     status = 0 if s.status == api.Status.Success else (1 if s.status == api.Status.UserInterrupt else -1)

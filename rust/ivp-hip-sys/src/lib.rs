@@ -120,6 +120,20 @@ pub struct ivp_batch_result_t {
     pub log_offsets: *const u64,
 }
 
+/// The `RADAU` struct's fields `solve_ivp` cannot reach (radau.rs:19-66); fill with `ivp_radau_settings_default`.
+#[repr(C)]
+pub struct ivp_radau_settings_t {
+    pub uround: f64,
+    pub safety_factor: f64,
+    pub scale_min: f64,
+    pub scale_max: f64,
+    pub newton_tol: f64,
+    pub newton_maxiter: i32,
+    pub has_newton_tol: i32,
+    pub predictive: i32,
+    pub reserved: i32,
+}
+
 #[repr(C)]
 pub struct ivp_run_stats_t {
     pub launches: u32,
@@ -236,6 +250,17 @@ extern "C" {
                                    out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
     pub fn ivp_batch_poll(ctx: *mut ivp_ctx_t, done: *mut c_int) -> c_int;
     pub fn ivp_batch_wait(ctx: *mut ivp_ctx_t) -> c_int;
+    // Radau IIA(5), the direct per-method call (RADAU::builder()...build().solve(..)), n <= 8
+    pub fn ivp_radau_settings_default(settings: *mut ivp_radau_settings_t);
+    pub fn ivp_options_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, message: *mut c_char, message_len: usize) -> c_int;
+    pub fn ivp_radau_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,
+                           message: *mut c_char, message_len: usize) -> c_int;
+    pub fn ivp_radau_solve(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                           t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                           settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t) -> c_int;
+    pub fn ivp_radau_solve_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                  t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                  settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
     // Solution.t / Solution.y in ONE call and ONE integration (page pool + gather kernel)
     pub fn ivp_batch_solve_logged_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64,
                                          params: *const f64, t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize,

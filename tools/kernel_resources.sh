@@ -18,3 +18,5 @@ run bdf_fma     rk_bdf.hip -DIVP_FAST=1 &
 run group_strict rk_group.hip -DIVP_FAST=0 &
 run group_fma   rk_group.hip -DIVP_FAST=1 &
 wait
+run radau_strict rk_radau.hip -DIVP_FAST=0 &
+wait
