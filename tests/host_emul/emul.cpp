@@ -1,4 +1,5 @@
-// emul.cpp -- TEST-ONLY harness: runs the per-lane kernel bodies of ivp_amd/csrc/rk_core.h on the
+// emul.cpp -- TEST-ONLY harness: runs the per-lane kernel bodies of ivp_amd/csrc/rk_core.h (explicit RK),
+// bdf_core.h (BDF) and radau_core.h (Radau IIA(5), strict build only) on the
 // CPU, lane by lane, with the same init -> chunk -> chunk ... schedule the GPU launch loop uses.
 //
 // It exists because the authoring container has no GPU: it lets the `-m "not gpu"` tests check the
@@ -15,8 +16,33 @@
 #define IVP_NS ivp_emul
 #include "../../ivp_amd/csrc/rk_core.h"
 #include "../../ivp_amd/csrc/bdf_core.h"
+#include "../../ivp_amd/csrc/radau_core.h"
 
 using namespace ivp_emul;
+
+// TEST-ONLY right-hand sides: the dense linear system y' = A y with A (row-major) in the parameters, so that the host runs
+// the Radau body at every state width 1..8 (the product's built-in problems have N = 1, 2, 3 and 6).  Each row is summed
+// left to right, one multiply and one add per term.  The Jac form overrides IVP::jac with the constant matrix.
+template <int N_>
+struct RhsDenseLin {
+    enum { N = N_, P = N_ * N_, NE = 0 };
+    static IVP_HD void ode(double, const double *y, double *d, const double *p)
+    {
+        for (int i = 0; i < N; ++i) {
+            double s = p[i * N] * y[0];
+            for (int j = 1; j < N; ++j) s = s + p[i * N + j] * y[j];
+            d[i] = s;
+        }
+    }
+};
+template <int N_>
+struct RhsDenseLinJac : RhsDenseLin<N_> {
+    static IVP_HD void jac(double, const double *, double (&j)[N_][N_], const double *p)
+    {
+        for (int r = 0; r < N_; ++r)
+            for (int c = 0; c < N_; ++c) j[r][c] = p[r * N_ + c];
+    }
+};
 
 template <int M, class R, int FULL>
 static void run_all(IvpKArgs a, uint64_t *chunks_out)
@@ -67,7 +93,23 @@ static int run_rhs(int method, int full, const IvpKArgs &a, uint64_t *chunks)
     case 1: run_flavour<1, R>(full, a, chunks); return 0;
     case 2: run_flavour<2, R>(full, a, chunks); return 0;
     case 3: run_flavour<3, R>(full, a, chunks); return 0;
+#if !IVP_FAST   // Radau has a strict build only (rk_radau.hip); problems with event functions are rejected by the host
+    case 4: if constexpr (R::NE == 0) { run_flavour<4, R>(full, a, chunks); return 0; } else return -1;
+#endif
     case 5: run_flavour<5, R>(full, a, chunks); return 0;
+    }
+    return -1;
+}
+
+// the test-only systems: DOPRI5 (the degenerate-interval yardstick) and Radau
+template <class R>
+static int run_rhs_test(int method, int full, const IvpKArgs &a, uint64_t *chunks)
+{
+    switch (method) {
+    case 1: run_flavour<1, R>(full, a, chunks); return 0;
+#if !IVP_FAST
+    case 4: run_flavour<4, R>(full, a, chunks); return 0;
+#endif
     }
     return -1;
 }
@@ -79,13 +121,15 @@ extern "C" int emul_solve(int method, int rhs_id, int full, IvpKArgs *args, uint
     IvpKArgs a = *args;
     const size_t B = a.B;
     // scratch the library would own
+    // (Radau, as ivp_capi.cpp sizes it: rad_mat 4 n n B doubles behind bdf_jac, rad_cont (4 n + 2) B doubles behind bdf_d,
+    // two pivot words per trajectory behind bdf_piv; n <= 8)
     std::vector<double> k1(8 * B), facold(B), hlamb(B), t_last(B);
     std::vector<uint32_t> flags(B);
     std::vector<int32_t> next_idx(B);
     uint32_t err_flag = 0;
     a.err_flag = &err_flag;
-    std::vector<double> bdf_d(8 * 8 * B), bdf_jac(64 * B), bdf_lu(64 * B);
-    std::vector<uint32_t> bdf_piv(B);
+    std::vector<double> bdf_d(8 * 8 * B), bdf_jac(4 * 64 * B), bdf_lu(64 * B);
+    std::vector<uint32_t> bdf_piv(2 * B);
     std::vector<double> prev_event(4 * B);
     a.prev_event = prev_event.data();
     a.bdf_d = bdf_d.data(); a.bdf_jac = bdf_jac.data(); a.bdf_lu = bdf_lu.data(); a.bdf_piv = bdf_piv.data();
@@ -109,6 +153,16 @@ extern "C" int emul_solve(int method, int rhs_id, int full, IvpKArgs *args, uint
     case 13: rc = run_rhs<RhsCannon>(method, full, a, chunks); break;
     case 14: rc = run_rhs<RhsRationalEv>(method, full, a, chunks); break;
     case 15: rc = run_rhs<RhsRobertsonJac>(method, full, a, chunks); break;
+    case 16: rc = run_rhs_test<RhsDenseLin<2>>(method, full, a, chunks); break;
+    case 17: rc = run_rhs_test<RhsDenseLinJac<2>>(method, full, a, chunks); break;
+    case 18: rc = run_rhs_test<RhsDenseLin<4>>(method, full, a, chunks); break;
+    case 19: rc = run_rhs_test<RhsDenseLinJac<4>>(method, full, a, chunks); break;
+    case 20: rc = run_rhs_test<RhsDenseLin<5>>(method, full, a, chunks); break;
+    case 21: rc = run_rhs_test<RhsDenseLinJac<5>>(method, full, a, chunks); break;
+    case 22: rc = run_rhs_test<RhsDenseLin<7>>(method, full, a, chunks); break;
+    case 23: rc = run_rhs_test<RhsDenseLinJac<7>>(method, full, a, chunks); break;
+    case 24: rc = run_rhs_test<RhsDenseLin<8>>(method, full, a, chunks); break;
+    case 25: rc = run_rhs_test<RhsDenseLinJac<8>>(method, full, a, chunks); break;
     }
     if (rc == 0 && (err_flag & 0x1u)) return -5;  // IVP_ERR_INVALID_STEP_SIZE
     return rc;
@@ -159,5 +213,50 @@ extern "C" void emul_pow3(const double *x, const double *e, double *r3, double *
     ivp_pow3(xs, es, out);
     for (int i = 0; i < 3; ++i) { r3[i] = out[i]; r1[i] = ivp_pow(x[i], e[i]); }
 }
+
+#if !IVP_FAST
+// The linear algebra of the Radau attempt on matrices the caller chooses -- what tests/helpers/radau_lu_probe.hip runs on the
+// device, with the same layout: nmat row-major blocks a / ar / ai [n * n] and right-hand sides b / br / bi [n], factors and
+// solutions in place, a right-hand side solved only where the factorisation reports ok.
+template <int N>
+static void radau_lu_run(double *a_all, double *b_all, uint32_t *piv_all, int *ok_all, double *ar_all, double *ai_all, double *br_all,
+                         double *bi_all, uint32_t *pivc_all, int *okc_all, int nmat)
+{
+    for (int q = 0; q < nmat; ++q) {
+        const size_t m0 = (size_t)q * (N * N), v0 = (size_t)q * N;
+        double a[N][N], b[N], ar[N][N], ai[N][N], br[N], bi[N];
+        for (int r = 0; r < N; ++r) {
+            b[r] = b_all[v0 + r]; br[r] = br_all[v0 + r]; bi[r] = bi_all[v0 + r];
+            for (int c = 0; c < N; ++c) { a[r][c] = a_all[m0 + r * N + c]; ar[r][c] = ar_all[m0 + r * N + c]; ai[r][c] = ai_all[m0 + r * N + c]; }
+        }
+        uint32_t piv, pivc;
+        const bool ok = bdf_lu_decomp<N>(a, piv);
+        if (ok) radau_lin_solve<N>(a, b, piv);
+        const bool okc = radau_lu_decomp_complex<N>(ar, ai, pivc);
+        if (okc) radau_lin_solve_complex<N>(ar, ai, br, bi, pivc);
+        for (int r = 0; r < N; ++r) {
+            b_all[v0 + r] = b[r]; br_all[v0 + r] = br[r]; bi_all[v0 + r] = bi[r];
+            for (int c = 0; c < N; ++c) { a_all[m0 + r * N + c] = a[r][c]; ar_all[m0 + r * N + c] = ar[r][c]; ai_all[m0 + r * N + c] = ai[r][c]; }
+        }
+        piv_all[q] = piv; ok_all[q] = ok ? 1 : 0; pivc_all[q] = pivc; okc_all[q] = okc ? 1 : 0;
+    }
+}
+
+extern "C" int emul_radau_lu(int n, double *a, double *b, uint32_t *piv, int *ok, double *ar, double *ai, double *br, double *bi,
+                             uint32_t *pivc, int *okc, int nmat)
+{
+    switch (n) {
+    case 1: radau_lu_run<1>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 2: radau_lu_run<2>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 3: radau_lu_run<3>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 4: radau_lu_run<4>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 5: radau_lu_run<5>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 6: radau_lu_run<6>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 7: radau_lu_run<7>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    case 8: radau_lu_run<8>(a, b, piv, ok, ar, ai, br, bi, pivc, okc, nmat); return 0;
+    }
+    return -1;
+}
+#endif
 
 extern "C" size_t emul_kargs_size(void) { return sizeof(IvpKArgs); }

@@ -1,5 +1,6 @@
 """TEST-ONLY driver of tests/host_emul/libemul_{strict,fast}.so (see emul.cpp): runs the per-lane
-kernel bodies of ivp_amd/csrc/rk_core.h on the CPU with the GPU launch loop's chunk schedule."""
+kernel bodies of ivp_amd/csrc/rk_core.h, bdf_core.h and radau_core.h (Radau: strict library only) on the CPU with the
+GPU launch loop's chunk schedule."""
 import ctypes as C
 import os
 import subprocess
@@ -53,16 +54,27 @@ LOG_ALLOC_STRIDE = 16
 
 _libs = {}
 RHS = {"decay": 0, "sho": 1, "vdp": 2, "cr3bp": 3, "lorenz": 4, "zero": 5, "rational": 6, "exp2": 7,
-       "linear": 8, "robertson": 9, "vdp_eps": 10, "sho_ev": 11, "ball": 12, "cannon": 13, "rational_ev": 14, "robertson_jac": 15}
+       "linear": 8, "robertson": 9, "vdp_eps": 10, "sho_ev": 11, "ball": 12, "cannon": 13, "rational_ev": 14, "robertson_jac": 15,
+       # test-only dense linear systems y' = A y of emul.cpp (A row-major in the parameters), without / with an analytic jac:
+       # DOPRI5 and RADAU only
+       "lin2": 16, "lin2_jac": 17, "lin4": 18, "lin4_jac": 19, "lin5": 20, "lin5_jac": 21, "lin7": 22, "lin7_jac": 23,
+       "lin8": 24, "lin8_jac": 25}
 RHS_DIMS = {0: (1, 1), 1: (2, 0), 2: (2, 1), 3: (6, 1), 4: (3, 3), 5: (3, 0), 6: (2, 0), 7: (2, 0),
-            8: (2, 0), 9: (3, 0), 10: (2, 1), 11: (2, 0), 12: (2, 2), 13: (2, 0), 14: (2, 0)}
+            8: (2, 0), 9: (3, 0), 10: (2, 1), 11: (2, 0), 12: (2, 2), 13: (2, 0), 14: (2, 0), 15: (3, 0),
+            16: (2, 4), 17: (2, 4), 18: (4, 16), 19: (4, 16), 20: (5, 25), 21: (5, 25), 22: (7, 49), 23: (7, 49),
+            24: (8, 64), 25: (8, 64)}
 RHS_NE = {11: 1, 12: 1, 13: 1, 14: 3}
-METHODS = {"RK23": 0, "DOPRI5": 1, "RK45": 1, "DOP853": 2, "RK4": 3, "BDF": 5}
-NCOEF = {0: 4, 1: 5, 2: 8, 3: 4, 5: 7}
+METHODS = {"RK23": 0, "DOPRI5": 1, "RK45": 1, "DOP853": 2, "RK4": 3, "RADAU": 4, "BDF": 5}
+NCOEF = {0: 4, 1: 5, 2: 8, 3: 4, 4: 4, 5: 7}
+# struct RADAU's own fields (ivp_radau_settings_default in ivp_capi.cpp) and the bits of ctl_nstiff (radau_core.h)
+RADAU_DEFAULTS = {"newton_maxiter": 7, "newton_tol": None, "predictive": True, "uround": 2.3e-16, "safety_factor": 0.9,
+                  "scale_min": 0.2, "scale_max": 8.0}
+IVP_RAD_HAS_NEWTON_TOL = 0x100
+IVP_RAD_PREDICTIVE = 0x200
 
 
 def build():
-    subprocess.check_call(["make", "-C", _HERE], stdout=subprocess.DEVNULL)
+    subprocess.check_call(["make", "-j2", "-C", _HERE], stdout=subprocess.DEVNULL)
 
 
 def lib(fast=False):
@@ -81,8 +93,11 @@ def lib(fast=False):
 
 def solve_batch(rhs, y0, params, t0, t1, *, method="DOPRI5", rtol=1e-3, atol=1e-6, max_steps=None, t_eval=None,
                 first_step=None, max_step=None, min_step=None, dense_output=False, max_log=0, chunk=64, fast=False,
-                event_direction=None, event_terminal=None, max_events=16, settings=None, paged_log=None, flavour_log_only=True, defer_eval=True, defer_events=True):
-    """``paged_log=pool_doubles``: the one-pass step log -- records go to wave pages in a pool of that many doubles, chained
+                event_direction=None, event_terminal=None, max_events=16, settings=None, paged_log=None, flavour_log_only=True, defer_eval=True, defer_events=True,
+                radau=None):
+    """``radau``: the fields of ``struct RADAU`` for ``method="RADAU"`` (a dict with any of RADAU_DEFAULTS' keys), laid into
+    the argument block the way ``submit_impl`` does for ``ivp_radau_solve``; the explicit methods' ``settings`` do not apply.
+    ``paged_log=pool_doubles``: the one-pass step log -- records go to wave pages in a pool of that many doubles, chained
     per trajectory (ivp_kargs.h; on the host a "wave" is one lane, so every page has one column); ``res['log_pool']``,
     ``res['log_cur']``, ``res['log_used']`` (doubles) and ``res['log_overflow']`` come back next to ``n_log``
     (``gather_pages`` below lays them out as the CSR log)."""
@@ -122,6 +137,18 @@ def solve_batch(rhs, y0, params, t0, t1, *, method="DOPRI5", rtol=1e-3, atol=1e-
     a.has_ctl = int(settings is not None)
     if settings is not None and max_steps is None:
         a.nmax = 10_000 if m == 0 else 100_000
+    if m == 4:   # submit_impl's `if (rad)` block: the RADAU struct's fields where radau_core.h reads them
+        assert settings is None and not fast, "Radau: its own struct (radau=...), strict arithmetic only"
+        rd = {**RADAU_DEFAULTS, **(radau or {})}
+        assert set(rd) == set(RADAU_DEFAULTS), sorted(set(rd) - set(RADAU_DEFAULTS))
+        a.ctl_uround, a.ctl_safety = float(rd["uround"]), float(rd["safety_factor"])
+        a.ctl_facc1, a.ctl_facc2 = 1.0 / float(rd["scale_min"]), 1.0 / float(rd["scale_max"])
+        a.ctl_beta = 0.0 if rd["newton_tol"] is None else float(rd["newton_tol"])
+        a.ctl_nstiff = int(rd["newton_maxiter"]) | (IVP_RAD_HAS_NEWTON_TOL if rd["newton_tol"] is not None else 0) | \
+            (IVP_RAD_PREDICTIVE if rd["predictive"] else 0)
+        a.has_ctl = 0
+    else:
+        assert radau is None, "radau= goes with method='RADAU'"
     res = {
         "y_end": np.zeros((n, B)), "t_end": np.zeros(B), "h_next": np.zeros(B), "status": np.zeros(B, dtype=np.int32),
         "nfev": np.zeros(B, dtype=np.uint64), "nstep": np.zeros(B, dtype=np.uint64),
@@ -191,7 +218,7 @@ def solve_batch(rhs, y0, params, t0, t1, *, method="DOPRI5", rtol=1e-3, atol=1e-
     # the library's choice of kernel flavour (ivp_capi.cpp): log-only when every accepted step is recorded and nothing else is
     # asked of the device DefaultSolOut
     log_only = full and t_eval is None and not dense_output and ne_ev == 0 and first_step is None and (max_log > 0 or paged_log is not None)
-    flavour = 2 if (log_only and flavour_log_only) else int(full)
+    flavour = 2 if (log_only and flavour_log_only and m != 4) else int(full)
     # ... deferred t_eval sampling (flavour 3): DOP853 with t_eval and nothing else asked of the device DefaultSolOut
     if m == 2 and t_eval is not None and len(np.atleast_1d(t_eval)) > 0 and not dense_output and ne_ev == 0 and defer_eval:
         flavour = 3
@@ -213,6 +240,23 @@ def solve_batch(rhs, y0, params, t0, t1, *, method="DOPRI5", rtol=1e-3, atol=1e-
         res["log_used"] = int(used.sum())
         res["log_overflow"] = bool((used > res["log_region"]).any())
     return res
+
+
+def radau_lu(n, ref):
+    """emul_radau_lu on the systems of tests/radau_lu_cases.reference(n): the host twin of tests/helpers/radau_lu_probe.hip,
+    with the probe's result layout."""
+    L = lib(False)
+    nm = len(ref)
+    blk = lambda key, shape: np.ascontiguousarray(np.stack([r[key] for r in ref]).reshape(shape), dtype=np.float64)
+    a, ar, ai = (blk(k, (nm, n * n)) for k in ("a", "ar", "ai"))
+    b, br, bi = (blk(k, (nm, n)) for k in ("b", "br", "bi"))
+    piv, pivc = np.full(nm, 0xFFFFFFFF, dtype=np.uint32), np.full(nm, 0xFFFFFFFF, dtype=np.uint32)
+    ok, okc = np.full(nm, -1, dtype=np.int32), np.full(nm, -1, dtype=np.int32)
+    L.emul_radau_lu.restype = C.c_int
+    L.emul_radau_lu.argtypes = [C.c_int] + [VP] * 10 + [C.c_int]
+    p = lambda arr: arr.ctypes.data_as(VP)
+    assert L.emul_radau_lu(n, p(a), p(b), p(piv), p(ok), p(ar), p(ai), p(br), p(bi), p(pivc), p(okc), nm) == 0
+    return dict(f=a.reshape(nm, n, n), x=b, piv=piv, ok=ok, fr=ar.reshape(nm, n, n), fi=ai.reshape(nm, n, n), xr=br, xi=bi, pivc=pivc, okc=okc)
 
 
 LOG_SLOTS = 32

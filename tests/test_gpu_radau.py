@@ -467,3 +467,226 @@ def test_options_method_radau_through_solve_ivp_batch_is_still_unsupported():
     with pytest.raises(ivp_amd.ConfigError) as e:
         ivp_amd.solve_ivp_batch(ivp_amd.SHO(), 0.0, 1.0, np.array([[1.0], [0.0]]), None, Options(method="RADAU"))
     assert e.value.code == -101
+
+
+# ---- 11. the branches no whole solve above takes ------------------------------------------------------------------------
+# The same inputs run on the host in tests/test_radau_emul_cpu.py; what only the device can show is the hiprtc
+# instantiations, the launch loop's own bookkeeping across restarts and retired lanes, and the compiled kernels' bits.
+
+def lin_matrix(n):
+    """_a8()'s construction at width n (tests/test_radau_emul_cpu.py has the same)."""
+    a = [[1e-3 * (1 + ((3 * i + 5 * j) % 7)) for j in range(n)] for i in range(n)]
+    for i in range(n):
+        a[i][i] = -1.0 - 0.25 * i
+        if i % 2:
+            a[i][i - 1] = 200.0
+    return a
+
+
+def lin_source(a, with_jac):
+    """y' = A y with A fixed in the functor, every row summed left to right (M.rhs_dense_linear)."""
+    n = len(a)
+    lit = lambda v: float(v).hex()
+    src = "__device__ void ode(double x, const double* y, double* d, const double* p) {\n"
+    for i in range(n):
+        src += f"  d[{i}] = " + " + ".join(f"{lit(a[i][j])} * y[{j}]" for j in range(n)) + ";\n"
+    src += "}\n"
+    if with_jac:
+        src += "__device__ void jac(double x, const double* y, double* j, const double* p) {\n"
+        src += "".join(f"  j[{i * n + k}] = {lit(a[i][k])};\n" for i in range(n) for k in range(n)) + "}\n"
+    return src
+
+
+# n = 2, the matrix in the parameters: one compiled problem serves every 2 x 2 Jacobian below
+LIN2_SRC = ("__device__ void ode(double x, const double* y, double* d, const double* p) { d[0] = p[0] * y[0] + p[1] * y[1]; d[1] = p[2] * y[0] + p[3] * y[1]; }\n"
+            "__device__ void jac(double x, const double* y, double* j, const double* p) { j[0] = p[0]; j[1] = p[1]; j[2] = p[2]; j[3] = p[3]; }\n")
+
+
+def lin_models(a, y0s, t1, with_jac, rtol=RT, atol=AT, **kw):
+    return [M.solve(M.rhs_dense_linear(a), 0.0, t1, list(y0), rtol, atol, jac=M.jac_dense_linear(a) if with_jac else None, **kw) for y0 in y0s]
+
+
+def test_newton_maxiter_1_is_status_singular_matrix_after_five_restarts():
+    y0, eps = vdp_eps_batch()
+    y0, eps = np.ascontiguousarray(y0[:, :3]), np.ascontiguousarray(eps[:, :3])
+    models = [M.solve(M.rhs_vdp_eps(float(eps[0, b])), 0.0, 2.0, [float(v) for v in y0[:, b]], RT, AT, settings=M.Settings(newton_maxiter=1)) for b in range(3)]
+    assert all(m.status == M.SINGULAR_MATRIX and m.n_restart == 5 and m.n_restart_newton == 6 and m.naccpt == 0 for m in models)
+    for chunk in (0, 1):
+        r = Radau(newton_maxiter=1).solve_batch(ivp_amd.StiffVanDerPol(), 0.0, 2.0, y0, eps, Options(rtol=RT, atol=AT, chunk_attempts=chunk))
+        assert_rows(r, models, f"newton_maxiter = 1, chunk_attempts = {chunk}")
+        assert all(int(v) == ivp_amd.Status.SingularMatrix == 5 for v in _np(r.status))
+
+
+def test_newton_maxiter_2_restarts_survive_every_launch_boundary():
+    """chunk_attempts = 1: h, reject, call_decomp and singular_count (flag bits 8..10) cross a launch boundary after every
+    one of hundreds of restarts; the solve succeeds only because every accepted step resets the count.  (A count lost at a
+    boundary shows in the newton_maxiter = 1 test above at chunk_attempts = 1: its fifth restart must still end the solve.)"""
+    y0, eps = vdp_eps_batch()
+    y0, eps = np.ascontiguousarray(y0[:, :2]), np.ascontiguousarray(eps[:, :2])
+    models = [M.solve(M.rhs_vdp_eps(float(eps[0, b])), 0.0, 2.0, [float(v) for v in y0[:, b]], RT, AT, settings=M.Settings(newton_maxiter=2)) for b in range(2)]
+    assert all(m.n_restart_newton > 100 and m.naccpt > 0 for m in models)
+    r = Radau(newton_maxiter=2).solve_batch(ivp_amd.StiffVanDerPol(), 0.0, 2.0, y0, eps, Options(rtol=RT, atol=AT, chunk_attempts=1))
+    assert_rows(r, models, "newton_maxiter = 2, chunk_attempts = 1")
+
+
+def test_real_zero_pivot_on_the_first_factorisation():
+    """Built-in decay (y' = -k y) with k = -(U1 / h): E1 = U1 / h - J is exactly zero; for y0 in {0, 2^-26, -2^-27} the
+    forward-difference Jacobian is exact (see tests/test_radau_emul_cpu.py)."""
+    h = 0.01
+    k = -(M.U1 / h)
+    y0s = [0.0, 2.0 ** -26, -(2.0 ** -27)]
+    models = [M.solve(M.rhs_decay(k), 0.0, 0.05, [v], RT, AT, first_step=h) for v in y0s]
+    assert all(m.n_restart_real == 1 and m.n_restart == 1 and m.status == M.SUCCESS and m.h_tried[0] == 0.5 * h for m in models)
+    r = Radau().solve_batch(ivp_amd.ExponentialDecay(), 0.0, 0.05, np.array([y0s]), np.full((1, 3), k), Options(rtol=RT, atol=AT, first_step=h))
+    assert_rows(r, models, "real zero pivot")
+
+
+def _lin2(J, y0s, t1, h):
+    flat = [J[0][0], J[0][1], J[1][0], J[1][1]]
+    models = lin_models(J, y0s, t1, True, first_step=h)
+    prob = ivp_amd.DeviceIVP(LIN2_SRC, 2, params=flat, jac=True)
+    r = Radau().solve_batch(prob, 0.0, t1, np.array(y0s).T.copy(), None, Options(rtol=RT, atol=AT, first_step=h))
+    return models, r
+
+
+def test_complex_zero_pivot_on_the_first_factorisation():
+    """The rotation J = [[a, -b], [b, a]], a = ALPH / h, b = BETA / h: E2 = [[i b, b], [-b, i b]], second pivot exactly zero."""
+    h = 2.0 ** -6
+    a, b = M.ALPH / h, M.BETA / h
+    models, r = _lin2([[a, -b], [b, a]], [[1.0, 0.0], [0.3, -0.7]], 4.0 * h, h)
+    assert all(m.n_restart_complex == 1 and m.n_restart == 1 and m.n_restart_real == 0 and m.h_tried[0] == 0.5 * h for m in models)
+    assert_rows(r, models, "complex zero pivot")
+
+
+def test_purely_imaginary_multiplier_in_the_complex_elimination():
+    h = 2.0 ** -10
+    models, r = _lin2([[0.0, 1.0], [-1e5, M.ALPH / h]], [[1.0, 0.0], [0.5, 0.25]], 8.0 * h, h)
+    assert all("imag" in m.cases and ("complex", 0, 1) in m.pivots for m in models)
+    assert_rows(r, models, "imaginary multiplier")
+
+
+def test_max_step_bounds_every_step():
+    y0 = np.array([[1.0, 0.3], [0.0, -0.7]])
+    models = [M.solve(M.rhs_sho, 0.0, 1.0, [float(v) for v in y0[:, b]], RT, AT, max_step=0.02) for b in range(2)]
+    free = M.solve(M.rhs_sho, 0.0, 1.0, [1.0, 0.0], RT, AT)
+    assert max(abs(v) for v in free.h_tried) > 0.04 and all(max(abs(v) for v in m.h_tried) == 0.02 for m in models)
+    r = Radau().solve_batch(ivp_amd.SHO(), 0.0, 1.0, y0, None, Options(rtol=RT, atol=AT, max_step=0.02, max_log=80))
+    assert_rows(r, models, "max_step")
+    for b, m in enumerate(models):
+        k = int(r.n_log[b])
+        assert k == len(m.t) <= 80 and all(same(r.t_log[q, b], m.t[q]) for q in range(k))
+        assert max(abs(float(r.t_log[q + 1, b]) - float(r.t_log[q, b])) for q in range(k - 1)) <= 0.02 * (1 + 1e-12)
+
+
+def test_min_step_with_max_step():
+    y0, eps = vdp_eps_batch()
+    y0, eps = np.ascontiguousarray(y0[:, :2]), np.ascontiguousarray(eps[:, :2])
+    models = vdp_eps_models(2, min_step=1e-3, max_step=0.02)
+    free = vdp_eps_models(2)
+    assert all(min(f.h_tried) < 1e-3 and max(f.h_tried) > 0.02 and m.h_tried.count(1e-3) > 0 and m.h_tried.count(0.02) > 0 for m, f in zip(models, free))
+    r = Radau().solve_batch(ivp_amd.StiffVanDerPol(), 0.0, 2.0, y0, eps, Options(rtol=RT, atol=AT, min_step=1e-3, max_step=0.02))
+    assert_rows(r, models, "min_step with max_step")
+
+
+@pytest.mark.parametrize("t1", [1.0, -1.0])
+def test_first_step_larger_than_max_step_is_clamped(t1):
+    m = M.solve(M.rhs_sho, 0.0, t1, [1.0, 0.0], RT, AT, first_step=0.5, max_step=0.01)
+    assert m.h_tried[0] == math.copysign(0.01, t1) and m.status == M.SUCCESS
+    r = Radau().solve_batch(ivp_amd.SHO(), 0.0, t1, np.array([[1.0], [0.0]]), None, Options(rtol=RT, atol=AT, first_step=0.5, max_step=0.01))
+    assert_rows(r, [m], "first_step > max_step")
+
+
+@pytest.mark.parametrize("analytic", [False, True])
+def test_vector_tolerances_and_the_same_vectors_reversed(analytic):
+    rt, at = [1e-4, 1e-7, 1e-5], [1e-6, 1e-11, 1e-8]
+    jac = M.jac_robertson if analytic else None
+    fwd = M.solve(M.rhs_robertson, 0.0, 1e3, [1.0, 0.0, 0.0], rt, at, jac=jac)
+    rev = M.solve(M.rhs_robertson, 0.0, 1e3, [1.0, 0.0, 0.0], rt[::-1], at[::-1], jac=jac)
+    assert fwd.status == rev.status == M.SUCCESS and (fwd.nstep, fwd.nfev, fwd.y_end) != (rev.nstep, rev.nfev, rev.y_end)
+    f = ivp_amd.RobertsonJac() if analytic else ivp_amd.Robertson()
+    y0 = np.array([[1.0], [0.0], [0.0]])
+    assert_rows(Radau().solve_batch(f, 0.0, 1e3, y0, None, Options(rtol=rt, atol=at)), [fwd], "vector tolerances")
+    assert_rows(Radau().solve_batch(f, 0.0, 1e3, y0, None, Options(rtol=rt[::-1], atol=at[::-1])), [rev], "vector tolerances reversed")
+
+
+@pytest.mark.parametrize("with_jac", [True, False])
+@pytest.mark.parametrize("n", [4, 5, 7])
+def test_state_widths_4_5_7_through_hiprtc(n, with_jac):
+    a = lin_matrix(n)
+    y0 = [1.0, 0.5, -0.5, 0.25, 0.0, 1e-3, -1.0, 2.0][:n]
+    y0s = [y0, [v + 1e-3 * (i + 1) for i, v in enumerate(y0)]]
+    models = lin_models(a, y0s, 5.0, with_jac, 1e-4, 1e-6)
+    assert all(m.status == 0 and any(p[0] == "real" for p in m.pivots) and any(p[0] == "complex" for p in m.pivots) for m in models)
+    prob = ivp_amd.DeviceIVP(lin_source(a, with_jac), n, jac=with_jac)
+    r = Radau().solve_batch(prob, 0.0, 5.0, np.array(y0s).T.copy(), None, Options(rtol=1e-4, atol=1e-6))
+    assert_rows(r, models, f"{n} x {n} linear system")
+
+
+def test_t_eval_and_dense_output_at_n8_through_hiprtc():
+    """A dense segment at N = 8 is 32 doubles per trajectory: the widest indexing of seg_cont."""
+    a = _a8()
+    y0s = [[1.0, 0.5, -0.5, 0.25, 0.0, 1e-3, -1.0, 2.0], [0.5] * 8]
+    y0 = np.array(y0s).T.copy()
+    prob = ivp_amd.DeviceIVP(_a8_source(True), 8, jac=True)
+    grid = [0.0, 0.1, 0.1 + 1e-13, 0.7, 1.5, 3.0, 3.5]
+    models = lin_models(a, y0s, 3.0, True, t_eval=grid)
+    r = Radau().solve_batch(prob, 0.0, 3.0, y0, None, Options(rtol=RT, atol=AT, t_eval=grid))
+    assert_rows(r, models, "n = 8, t_eval")
+    for b, m in enumerate(models):
+        k = int(r.n_filled[b])
+        assert k == len(m.t) == 6 and list(r.eval_idx[:k, b]) == m.eval_idx
+        assert all(same_vec(r.y_eval[q, :, b], m.y[q]) for q in range(k)), b
+    models = lin_models(a, y0s, 3.0, True, dense_output=True)
+    ml = max(len(m.segs) for m in models) + 1
+    r = Radau().solve_batch(prob, 0.0, 3.0, y0, None, Options(rtol=RT, atol=AT, dense_output=True, max_log=ml))
+    assert_rows(r, models, "n = 8, dense output")
+    for b, m in enumerate(models):
+        assert int(r.n_seg[b]) == len(m.segs) == m.naccpt > 3 and int(r.n_log[b]) == len(m.t)
+        for q, (cont, xold, h) in enumerate(m.segs):
+            assert same(r.seg_xold[q, b], xold) and same(r.seg_h[q, b], h) and same_vec(r.seg_cont[q, :, b], cont), (b, q)
+        assert all(same(r.t_log[q, b], m.t[q]) and same_vec(r.y_log[q, :, b], m.y[q]) for q in range(len(m.t))), b
+
+
+@pytest.mark.parametrize("flavour", ["end", "t_eval", "log", "dense"])
+def test_degenerate_and_nan_intervals_beside_five_healthy_trajectories(flavour):
+    """t1 == t0 and a NaN t1 retire in the init kernel with solve_ivp's own early return: status 0 / 3, h_next = 0, zero
+    counters, the t_eval points within 1e-12 of t0, one log record, the constant dense segment.  Held to what DOPRI5 (pinned
+    to the oracle) returns for the same lanes; the healthy neighbours stay the model's."""
+    y0 = np.array([[1.0, 0.5, 2.0, -0.3, -1.5, 2.0, 0.0], [0.0, 0.5, 0.25, 0.9, 1.0, -1.0, 1.0]])
+    t1s = np.array([3.0, 3.0, 0.0, 3.0, float("nan"), 2.0, 3.0])   # per-trajectory t1; lanes 2 and 4 are the odd ones
+    odd, healthy = {2: 0, 4: 3}, [0, 1, 3, 5, 6]
+    grid = [0.0, 5e-13, 0.1, 0.7, 1.5, 2.0, 3.0]
+    okw = {"end": {}, "t_eval": dict(t_eval=grid), "log": dict(max_log=6), "dense": dict(max_log=6, dense_output=True)}[flavour]
+    mkw = {"end": {}, "t_eval": dict(t_eval=grid), "log": {}, "dense": dict(dense_output=True)}[flavour]
+    models = {b: model(("degenerate", flavour, b), lambda b=b: M.solve(M.rhs_sho, 0.0, float(t1s[b]), [float(v) for v in y0[:, b]], RT, AT, **mkw)) for b in healthy}
+    r = Radau().solve_batch(ivp_amd.SHO(), 0.0, t1s, y0, None, Options(rtol=RT, atol=AT, **okw))
+    d = ivp_amd.solve_ivp_batch(ivp_amd.SHO(), 0.0, t1s, y0, None, Options(method="DOPRI5", rtol=RT, atol=AT, **okw))
+    for b in healthy:
+        g, w = gpu_row(r, b), model_row(models[b])
+        assert all(g[k] == w[k] for k in MEMBERS if k not in ("t_end", "h_next")) and same(g["t_end"], w["t_end"]) and \
+            same(g["h_next"], w["h_next"]) and same_vec(g["y_end"], w["y_end"]), (b, g, w)
+        m = models[b]
+        if flavour == "t_eval":
+            k = int(r.n_filled[b])
+            assert k == len(m.t) and list(r.eval_idx[:k, b]) == m.eval_idx and all(same_vec(r.y_eval[q, :, b], m.y[q]) for q in range(k)), b
+        elif flavour in ("log", "dense"):
+            assert int(r.n_log[b]) == len(m.t) > 6 and all(same(r.t_log[q, b], m.t[q]) and same_vec(r.y_log[q, :, b], m.y[q]) for q in range(6)), b
+    for b, status in odd.items():
+        g, w = gpu_row(r, b), gpu_row(d, b)
+        assert g["status"] == w["status"] == status and same(g["h_next"], 0.0) and same(g["h_next"], w["h_next"]), (b, g, w)
+        assert same(g["t_end"], w["t_end"]) and same(g["t_end"], 0.0) and same_vec(g["y_end"], w["y_end"]) and same_vec(g["y_end"], y0[:, b]), (b, g, w)
+        assert all(g[k] == 0 for k in ("nfev", "njev", "nlu", "nstep", "naccpt", "nrejct")) and all(w[k] == 0 for k in ("nfev", "nstep", "naccpt", "nrejct")), (b, g, w)
+        if flavour == "t_eval":
+            k = int(r.n_filled[b])
+            assert k == int(d.n_filled[b]) == (2 if status == 0 else 0), (b, k)
+            assert list(r.eval_idx[:k, b]) == list(d.eval_idx[:k, b]) and all(same_vec(r.y_eval[q, :, b], d.y_eval[q, :, b]) for q in range(k))
+        elif flavour in ("log", "dense"):
+            k = int(r.n_log[b])
+            assert k == int(d.n_log[b]) == (1 if status == 0 else 0), (b, k)
+            assert all(same(r.t_log[q, b], d.t_log[q, b]) and same_vec(r.y_log[q, :, b], d.y_log[q, :, b]) for q in range(k))
+        if flavour == "dense":
+            k = int(r.n_seg[b])
+            assert k == int(d.n_seg[b]) == (1 if status == 0 else 0), (b, k)
+            for q in range(k):   # ContinuousOutput::constant: [y, 0, 0, ..]; DOPRI5 carries 5 n coefficients, Radau 4 n
+                assert same(r.seg_xold[q, b], d.seg_xold[q, b]) and same(r.seg_h[q, b], d.seg_h[q, b])
+                assert same_vec(r.seg_cont[q, :, b], d.seg_cont[q, :8, b]) and same_vec(d.seg_cont[q, 8:, b], [0.0, 0.0])
