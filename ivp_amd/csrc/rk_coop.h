@@ -137,9 +137,13 @@ __device__ __forceinline__ double coop_sum(double term)
     return s;
 }
 
-// RhsCr3bp::ode_coop (declared and explained in rk_core.h next to the reference form)
-__device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const double *p)
+// RhsCr3bp::ode_coop (declared and explained in rk_core.h next to the reference form).  MODE 0: the plain operators; MODE 1
+// (IVP_COOP_INBAND builds only): the in-band helpers, this lane's r^2 and factor folded into acc; MODE 2: the plain
+// operators of a deferred stage block's second pass (the same statements as MODE 0).
+template <int MODE, class ACC>
+__device__ __forceinline__ double cr3bp_ode_coop(double ys, const double *p, ACC &acc)
 {
+    (void)acc;
     const uint32_t l = threadIdx.x & 7u;
     const bool hi = (l & 4u) != 0;
     const uint32_t i = l & 3u;                  // numerator role inside the quad: 0 -> a|b, 1 -> y, 2 -> z, 3 idle
@@ -159,19 +163,47 @@ __device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const do
     const double q1 = i == 0u ? X + mu : pos;
     double lin = fma(i == 0u ? 2.0 : -2.0, sw, pos);
     lin = i == 2u ? -0.0 : lin;
-    const double acc = fma(-g, q2, fma(-g1, q1, lin));
+    const double res = fma(-g, q2, fma(-g1, q1, lin));
 #else
-    const double r = sqrt(w * w + Y * Y + Z * Z);
-    const double r3 = r * r * r;
+    const double s = w * w + Y * Y + Z * Z;
     const double q = i == 0u ? w : pos;
-    const double T = (hi ? mu : 1.0 - mu) * q / r3;
+    const double n = (hi ? mu : 1.0 - mu) * q;
+    double T;
+#if IVP_COOP_INBAND
+    if constexpr (MODE == 1) {
+        // sufficiency as in rk_core.h (IvpInbandAcc): q is one of the w, y, z of this lane's own s; the idle lane's q is no operand
+        acc.smin = acc.smin < ivp_hi32(s) ? acc.smin : ivp_hi32(s);
+        acc.smax = acc.smax > ivp_hi32(s) ? acc.smax : ivp_hi32(s);
+        const int32_t e = i == 3u ? 0 : ivp_frexp_exp(q);
+        acc.emin = acc.emin < e ? acc.emin : e;
+        const double r = ivp_sqrt_inband(s);
+        T = ivp_div_inband(n, ivp_recip_inband(r * r * r));
+    } else
+#endif
+    {
+        const double r = sqrt(s);
+        const double r3 = r * r * r;
+        T = n / r3;
+    }
     const double T1 = lo_to_hi_only(T);         // upper quad: the first primary's term from the lane four below (the lower quad's result is replaced at the end)
     double lin = pos + (i == 0u ? 2.0 : -2.0) * sw;
     lin = i == 2u ? -0.0 : lin;
-    const double acc = (lin - T1) - T;
+    const double res = (lin - T1) - T;
 #endif
-    return hi_to_lo(acc, ys);                   // position lanes: d(pos)/dt = the velocity four lanes above
+    return hi_to_lo(res, ys);                   // position lanes: d(pos)/dt = the velocity four lanes above
 }
+__device__ __forceinline__ double RhsCr3bp::ode_coop(double, double ys, const double *p)
+{
+    IvpNoAcc none;
+    return cr3bp_ode_coop<0>(ys, p, none);
+}
+#if IVP_COOP_INBAND && !IVP_FAST
+template <bool INB, class ACC>
+__device__ __forceinline__ double RhsCr3bp::ode_coop_deferred(double, double ys, const double *p, ACC &acc)
+{
+    return cr3bp_ode_coop<INB ? 1 : 2>(ys, p, acc);
+}
+#endif
 
 template <class R, class = void>
 struct HasCoopOde { enum { v = 0 }; };
@@ -190,8 +222,22 @@ __device__ __forceinline__ double coop_ode(double t, double ystage, const double
     }
 }
 
+// the deferred guard for functors with an in-band lane-cooperative form (IVP_COOP_INBAND builds): what HasInbandOde looks for
+template <class R, class = void>
+struct CoopInband {};
+#if IVP_COOP_INBAND && !IVP_FAST
 template <class R>
-struct CoopRhs {
+struct CoopInband<R, decltype((void)&R::coop_inband_seed)> {
+    static __device__ __forceinline__ int32_t inband_seed(const double *p) { return R::coop_inband_seed(p); }
+    template <bool INB, class ACC>
+    static __device__ __forceinline__ void ode_deferred(double t, const double *ys, double *k, const double *p, ACC &acc)
+    {
+        k[0] = R::template ode_coop_deferred<INB>(t, ys[0], p, acc);
+    }
+};
+#endif
+template <class R>
+struct CoopRhs : CoopInband<R> {
     enum { NT = R::N, N = 1, P = R::P, NE = R::NE };
     static_assert(R::N <= 8, "eight lanes per trajectory");
     static __device__ __forceinline__ void ode(double t, const double *ys, double *k, const double *p) { k[0] = coop_ode<R>(t, ys[0], p); }

@@ -85,6 +85,15 @@
 #define KC_SCOPE_KZ(z) KC_SCOPE
 #define IVP_KZ_ARG 0ull
 #endif
+// KC_SCOPE_FROM(z): inside a helper that an attempt calls (the stage blocks): KC() goes on with the attempt's own XOR
+// partner, handed in as IVP_KZ_CUR, instead of defining another one
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KC_SCOPE_FROM(z) const uint64_t ivp_kz = (z); (void)ivp_kz;
+#define IVP_KZ_CUR ivp_kz
+#else
+#define KC_SCOPE_FROM(z) (void)(z);
+#define IVP_KZ_CUR 0ull
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define IVP_OPAQUE_V(v) asm volatile("" : "+v"(v))
 #else
@@ -172,6 +181,9 @@ IVP_HD double u2d(uint64_t u) { return __builtin_bit_cast(double, u); }
 #ifndef IVP_RHS_INBAND
 #define IVP_RHS_INBAND 1
 #endif
+#ifndef IVP_COOP_INBAND
+#define IVP_COOP_INBAND 0
+#endif
 struct IvpRecip { double d, r; };   // a denominator and (device) its refined reciprocal
 IVP_HD IvpRecip ivp_recip_inband(double d)
 {
@@ -233,6 +245,92 @@ IVP_HD bool ivp_wave_all(bool ok)
     return __builtin_amdgcn_ballot_w64(!ok) == 0;
 #else
     return ok;
+#endif
+}
+
+// ------------------------------------------------------------------------------------------------
+// The deferred guard of the DOPRI5 / DOP853 attempts.  A right-hand side with an in-band form (RhsCr3bp::ode_deferred)
+// is evaluated on the helpers above in EVERY stage without asking first; each call folds its operand ranges into three
+// per-lane 32-bit accumulators (IvpInbandAcc), and one ivp_wave_all after the last stage decides whether the wave keeps the
+// stage block or recomputes it with the plain operators.  Nothing is written before that decision, and a lane whose
+// operands were in band at every call holds the bits the plain operators give, so the redo changes nothing for it; an
+// out-of-band lane's helper values (garbage, but only arithmetic: no trap, no memory access) are discarded.
+//
+// The folded predicate is SUFFICIENT for the per-call one (ivp_sq_inband on s1, s2 and ivp_num_inband on the six products
+// c * f, c in {mu, 1 - mu}, f in {a, b, y, z}); it is not equal to it.  With hi(v) the high dword of v as an unsigned:
+//   (1) IVP_SQ_HI_LO <= hi(s) < IVP_SQ_HI_HI  =>  2^-200 <= s < 2^200.  For a double with the sign bit clear the bit
+//       pattern is monotone in the value, hi(2^-200) = (1023 - 200) << 20 and hi(2^200) = (1023 + 200) << 20; +-0 and
+//       denormals have hi < IVP_SQ_HI_LO, +inf and every NaN have hi >= 0x7FF00000, anything with the sign bit set has
+//       hi >= 0x80000000.  A running unsigned min / max over all s of the attempt tests both ends of all of them at once.
+//   (2) s = fl(fl(w * w + y * y) + z * z) is a sum of non-negative terms under a monotone rounding, so (1) gives
+//       w * w, y * y, z * z <= s < 2^200: w, y, z are finite and |w|, |y|, |z| <= 2^100 (w = a for s1, b for s2).
+//   (3) ivp_frexp_exp(f) >= -540 (the hardware's v_frexp_exp: 0 for +-0, +-inf and NaN, else e with |f| in
+//       [2^(e-1), 2^e))  =>  f is 0, or -- f being finite by (2) -- 2^-541 <= |f| <= 2^100.  A running signed min over
+//       the four factors of every call tests them all; the zeros (z = 0 on a planar orbit) pass it.
+//   (4) The coefficients are tested once per chunk (ivp_inband_seed): c is 0 or has ivp_frexp_exp(c) in [-50, 60],
+//       2^-51 <= |c| < 2^60.  A non-finite mu has exponent 0 there, but makes a = x + mu non-finite and fails (1).
+//   (5) So every product is +-0, or 2^-592 <= |c * f| < 2^160 exactly, far inside the normal range, and rounds to a value
+//       of [2^-592, 2^160], which lies in ivp_num_inband's [2^-601, 2^423).
+// tests/test_inband_deferred_cpu.py draws 2^20 states plus the edges and checks "folded => per call" on this host
+// restatement; tests/test_gpu_inband_deferred.py compares the device's answers with it on the same states.
+// ------------------------------------------------------------------------------------------------
+#define IVP_SQ_HI_LO 0x33700000u   // hi(2^-200)
+#define IVP_SQ_HI_HI 0x4C700000u   // hi(2^200)
+#define IVP_FACTOR_EXP_MIN (-540)
+struct IvpInbandAcc { uint32_t smin, smax; int32_t emin; };
+struct IvpNoAcc {};     // the plain pass of a deferred stage block: nothing to fold
+IVP_HD uint32_t ivp_hi32(double v) { return (uint32_t)(d2u(v) >> 32); }
+IVP_HD int32_t ivp_frexp_exp(double v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_frexp_exp(v);
+#else
+    int e = 0;
+    if (v == 0.0 || v != v || fabs(v) == __builtin_inf()) return 0;
+    (void)frexp(v, &e);
+    return e;
+#endif
+}
+// the per-chunk part, (4): the value every attempt's emin starts from -- 0 passes, the most negative int never does
+IVP_HD int32_t ivp_inband_seed(double c0, double c1)
+{
+    const int32_t e0 = ivp_frexp_exp(c0), e1 = ivp_frexp_exp(c1);
+    const bool ok = (c0 == 0.0 || (uint32_t)(e0 + 50) <= 110u) & (c1 == 0.0 || (uint32_t)(e1 + 50) <= 110u);
+    return ok ? 0 : -0x7FFFFFFF - 1;
+}
+IVP_HD IvpInbandAcc ivp_inband_begin(int32_t seed) { return {0xFFFFFFFFu, 0u, seed}; }
+IVP_HD uint32_t ivp_umin3(uint32_t a, uint32_t b, uint32_t c) { return a < (b < c ? b : c) ? a : (b < c ? b : c); }
+IVP_HD uint32_t ivp_umax3(uint32_t a, uint32_t b, uint32_t c) { return a > (b > c ? b : c) ? a : (b > c ? b : c); }
+IVP_HD int32_t ivp_imin3(int32_t a, int32_t b, int32_t c) { return a < (b < c ? b : c) ? a : (b < c ? b : c); }
+// one right-hand-side call: (1) on s1, s2 and (3) on a, b, y, z -- four v_frexp_exp, two v_min3, one v_min3_u32, one v_max3_u32
+IVP_HD void ivp_inband_fold(IvpInbandAcc &acc, double s1, double s2, double a, double b, double y, double z)
+{
+    acc.smin = ivp_umin3(acc.smin, ivp_hi32(s1), ivp_hi32(s2));
+    acc.smax = ivp_umax3(acc.smax, ivp_hi32(s1), ivp_hi32(s2));
+    acc.emin = ivp_imin3(ivp_imin3(acc.emin, ivp_frexp_exp(a), ivp_frexp_exp(b)), ivp_frexp_exp(y), ivp_frexp_exp(z));
+}
+IVP_HD void ivp_inband_fold(IvpNoAcc &, double, double, double, double, double, double) {}
+// the decision after the last stage.  IVP_INBAND_FORCE_REDO (tests/helpers/inband_redo_main.cpp) answers "out of band"
+// always, so that every attempt takes the redo.
+IVP_HD bool ivp_inband_ok(const IvpInbandAcc &acc)
+{
+#if defined(IVP_INBAND_FORCE_REDO)
+    (void)acc;
+    return false;
+#else
+    return (acc.smin >= IVP_SQ_HI_LO) & (acc.smax < IVP_SQ_HI_HI) & (acc.emin >= IVP_FACTOR_EXP_MIN);
+#endif
+}
+
+// A flag that is the same in every active lane of the wave (Lane::inb_plain: set by all of them at once, after one
+// ivp_wave_all), read as a scalar.  The compiler cannot see that through the attempt loop's divergent exits and would
+// branch on it with an exec mask; the first active lane's copy makes the branch a scalar one.
+IVP_HD bool ivp_wave_flag(bool v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane((int)v) != 0;
+#else
+    return v;
 #endif
 }
 
@@ -477,30 +575,65 @@ struct RhsCr3bp {    // examples/cr3bp.rs:23-36
         // d[3] = x + 2.0 * vy - (1.0 - mu) * (x + mu) / r13 - mu * (x - 1.0 + mu) / r23
         // d[4] = y - 2.0 * vx - (1.0 - mu) * y / r13 - mu * y / r23
         // d[5] = -(1.0 - mu) * z / r13 - mu * z / r23
-        const double s1 = a * a + y * y + z * z, s2 = b * b + y * y + z * z;
-        const double c1 = 1.0 - mu;
-        const double n3a = c1 * a, n3b = mu * b, n4a = c1 * y, n4b = mu * y, n5a = -c1 * z, n5b = mu * z;
-        const double l3 = x + 2.0 * vy, l4 = y - 2.0 * vx;
+        (void)y; (void)z;
+        const StrictTerms t = strict_terms(s, mu, a, b);
         d[0] = vx; d[1] = vy; d[2] = vz;
         // the whole wave in range (see ivp_recip_inband): one refined reciprocal per primary serves its three numerators
-        // (& rather than &&: straight-line compares, no exec-mask branches)
-        if (IVP_RHS_INBAND && ivp_wave_all(ivp_sq_inband(s1) & ivp_sq_inband(s2) & ivp_num_inband(n3a) & ivp_num_inband(n3b) &
-                         ivp_num_inband(n4a) & ivp_num_inband(n4b) & ivp_num_inband(n5a) & ivp_num_inband(n5b))) {
-            const double r1 = ivp_sqrt_inband(s1), r2 = ivp_sqrt_inband(s2);
-            const IvpRecip i13 = ivp_recip_inband(r1 * r1 * r1), i23 = ivp_recip_inband(r2 * r2 * r2);
-            d[3] = l3 - ivp_div_inband(n3a, i13) - ivp_div_inband(n3b, i23);
-            d[4] = l4 - ivp_div_inband(n4a, i13) - ivp_div_inband(n4b, i23);
-            d[5] = ivp_div_inband(n5a, i13) - ivp_div_inband(n5b, i23);
-        } else {   // a collision orbit, far away, tiny numerators, NaN / inf: the plain operators
-            const double r1 = sqrt(s1), r2 = sqrt(s2);
-            const double r13 = r1 * r1 * r1;  // powi(3)
-            const double r23 = r2 * r2 * r2;
-            d[3] = l3 - n3a / r13 - n3b / r23;
-            d[4] = l4 - n4a / r13 - n4b / r23;
-            d[5] = n5a / r13 - n5b / r23;
-        }
+        if (IVP_RHS_INBAND && ivp_wave_all(strict_inband(t))) strict_accel<true>(t, d);
+        else strict_accel<false>(t, d);   // a collision orbit, far away, tiny numerators, NaN / inf: the plain operators
 #endif
     }
+#if !IVP_FAST
+    struct StrictTerms { double s1, s2, n3a, n3b, n4a, n4b, n5a, n5b, l3, l4; };
+    static IVP_HD StrictTerms strict_terms(const double *s, double mu, double a, double b)
+    {
+        const double x = s[0], y = s[1], z = s[2], vx = s[3], vy = s[4];
+        const double s1 = a * a + y * y + z * z, s2 = b * b + y * y + z * z;
+        const double c1 = 1.0 - mu;
+        return {s1, s2, c1 * a, mu * b, c1 * y, mu * y, -c1 * z, mu * z, x + 2.0 * vy, y - 2.0 * vx};
+    }
+    // the per-call guard: what the folded one of ivp_inband_fold / ivp_inband_ok is sufficient for
+    static IVP_HD bool strict_inband(const StrictTerms &t)
+    {
+        // & on ints rather than &&: straight-line compares, no exec-mask branches
+        return ((int)ivp_sq_inband(t.s1) & (int)ivp_sq_inband(t.s2) & (int)ivp_num_inband(t.n3a) & (int)ivp_num_inband(t.n3b) &
+                (int)ivp_num_inband(t.n4a) & (int)ivp_num_inband(t.n4b) & (int)ivp_num_inband(t.n5a) & (int)ivp_num_inband(t.n5b)) != 0;
+    }
+    template <bool INB>
+    static IVP_HD void strict_accel(const StrictTerms &t, double *d)
+    {
+        if constexpr (INB) {
+            const double r1 = ivp_sqrt_inband(t.s1), r2 = ivp_sqrt_inband(t.s2);
+            const IvpRecip i13 = ivp_recip_inband(r1 * r1 * r1), i23 = ivp_recip_inband(r2 * r2 * r2);
+            d[3] = t.l3 - ivp_div_inband(t.n3a, i13) - ivp_div_inband(t.n3b, i23);
+            d[4] = t.l4 - ivp_div_inband(t.n4a, i13) - ivp_div_inband(t.n4b, i23);
+            d[5] = ivp_div_inband(t.n5a, i13) - ivp_div_inband(t.n5b, i23);
+        } else {
+            const double r1 = sqrt(t.s1), r2 = sqrt(t.s2);
+            const double r13 = r1 * r1 * r1;  // powi(3)
+            const double r23 = r2 * r2 * r2;
+            d[3] = t.l3 - t.n3a / r13 - t.n3b / r23;
+            d[4] = t.l4 - t.n4a / r13 - t.n4b / r23;
+            d[5] = t.n5a / r13 - t.n5b / r23;
+        }
+    }
+#if IVP_RHS_INBAND
+    // The in-band form for the deferred guard of dopri5_attempt / dop853_attempt (see IvpInbandAcc): INB = true runs the
+    // helpers without asking and folds this call's operand ranges into `acc`, INB = false is the plain expression.
+    template <bool INB, class ACC>
+    static IVP_HD void ode_deferred(double, const double *s, double *d, const double *p, ACC &acc)
+    {
+        const double mu = p[0];
+        const double a = s[0] + mu;
+        const double b = s[0] - 1.0 + mu;
+        const StrictTerms t = strict_terms(s, mu, a, b);
+        d[0] = s[3]; d[1] = s[4]; d[2] = s[5];
+        if constexpr (INB) ivp_inband_fold(acc, t.s1, t.s2, a, b, s[1], s[2]);
+        strict_accel<INB>(t, d);
+    }
+    static IVP_HD int32_t inband_seed(const double *p) { return ivp_inband_seed(p[0], 1.0 - p[0]); }
+#endif
+#endif
 #if defined(__HIPCC__)
     // Lane-cooperative form for rk_coop.h.  Layout inside the 8-lane group: lanes 0..2 hold x, y, z, lanes 4..6 hold
     // vx, vy, vz (lanes 3 and 7 idle), so that every exchange below is one DPP hop.  The two quads run ONE instruction
@@ -513,6 +646,13 @@ struct RhsCr3bp {    // examples/cr3bp.rs:23-36
     // zero result ((-s) * t == -(s * t) and (-s) / t == -(s / t) hold exactly in IEEE arithmetic).
     static constexpr int coop_lane_of(int c) { return c < 3 ? c : c + 1; }
     static __device__ __forceinline__ double ode_coop(double, double ys, const double *p);
+#if IVP_COOP_INBAND && !IVP_FAST
+    // Build switch IVP_COOP_INBAND = 1 (off in the product: measured slower, profiles/EXPERIMENTS.md section 4g): the
+    // lane-cooperative form under the deferred guard.  Each lane folds its own r^2 and its own factor q.
+    template <bool INB, class ACC>
+    static __device__ __forceinline__ double ode_coop_deferred(double, double ys, const double *p, ACC &acc);
+    static __device__ __forceinline__ int32_t coop_inband_seed(const double *p) { return ivp_inband_seed(p[0], 1.0 - p[0]); }
+#endif
 #endif
 };
 struct RhsLorenz {   // benches/benchmark.py:30-37
@@ -622,6 +762,19 @@ struct RhsRationalEv {   // tests/test_ivp.py:345-353
 //   NormOps<R>    NT = number of components in the RMS norms, sum() = the reference's left-to-right sum,
 //                 rtol(a, c) / atol(a, c) = tolerances of local component c
 // ------------------------------------------------------------------------------------------------
+// a right-hand side with an in-band form for the deferred guard (ode_deferred<INB>, inband_seed: see IvpInbandAcc)
+template <class R, class = void>
+struct HasInbandOde { enum { v = 0 }; };
+template <class R>
+struct HasInbandOde<R, decltype((void)&R::inband_seed)> { enum { v = 1 }; };
+// one stage's right-hand side inside a stage block: the in-band or the plain form of such a functor under the deferred
+// guard, R::ode otherwise
+template <class R, bool INB, class ACC>
+IVP_HD void stage_ode(double t, const double *y, double *d, const double *p, ACC &acc)
+{
+    if constexpr (HasInbandOde<R>::v) R::template ode_deferred<INB>(t, y, d, p, acc);
+    else R::ode(t, y, d, p);
+}
 template <int N>
 struct IdMap {
     enum { NT = N };
@@ -688,6 +841,10 @@ struct Lane {
     // deferred t_eval sampling (flavour 3): the next t_eval point of the trajectory (NaN: none left), so that an attempt whose
     // step holds no sample decides that from registers -- a load from the grid in every attempt sat on every wave's path
     double t_next;
+    // deferred guard (HasInbandOde right-hand sides): the per-chunk part of the predicate (ivp_inband_seed), and the
+    // wave-uniform "an attempt of this chunk had to be redone: stay on the plain operators"
+    int32_t inb_seed;
+    bool inb_plain;
 };
 
 // The t_eval grid of trajectory j: the batch's shared grid, or -- every reference solve_ivp() call has its own
@@ -1698,6 +1855,96 @@ IVP_HD bool stiff_tick(const IvpKArgs &a, uint32_t j, uint32_t &flags, uint32_t 
 // direct method call (CTL = true)
 #define IVP_CTL(field, dflt) (CTL ? a.field : KC(dflt))
 
+// tableau, dopri5.rs:482-520
+namespace dopri5_tab {
+constexpr double C2 = 0.2, C3 = 0.3, C4 = 0.8, C5 = 8.0 / 9.0;
+constexpr double A21 = 0.2, A31 = 3.0 / 40.0, A32 = 9.0 / 40.0;
+constexpr double A41 = 44.0 / 45.0, A42 = -56.0 / 15.0, A43 = 32.0 / 9.0;
+constexpr double A51 = 19372.0 / 6561.0, A52 = -25360.0 / 2187.0, A53 = 64448.0 / 6561.0, A54 = -212.0 / 729.0;
+constexpr double A61 = 9017.0 / 3168.0, A62 = -355.0 / 33.0, A63 = 46732.0 / 5247.0, A64 = 49.0 / 176.0, A65 = -5103.0 / 18656.0;
+constexpr double A71 = 35.0 / 384.0, A73 = 500.0 / 1113.0, A74 = 125.0 / 192.0, A75 = -2187.0 / 6784.0, A76 = 11.0 / 84.0;
+constexpr double E1 = 71.0 / 57600.0, E3 = -71.0 / 16695.0, E4 = 71.0 / 1920.0, E5 = -17253.0 / 339200.0, E6 = 22.0 / 525.0, E7 = -1.0 / 40.0;
+constexpr double D1 = -12715105075.0 / 11282082432.0, D3 = 87487479700.0 / 32700410799.0, D4 = -10690763975.0 / 1880347072.0,
+                 D5 = 701980252875.0 / 199316789632.0, D6 = -1453857185.0 / 822651844.0, D7 = 69997945.0 / 29380423.0;
+}  // namespace dopri5_tab
+
+// The statements of the DOPRI5 stage block, with the right-hand-side call left open: ODE(t, y_in, k_out).  Written once and
+// expanded in the attempts themselves (R::ode: right-hand sides without an in-band form and the kernels that do not defer,
+// whose instruction stream is what it always was) and in dopri5_stages (the two forms of the deferred guard).  Names of the
+// enclosing scope: x, h, xph, y, k1, k2 .. k6, y1, N and the tableau.
+#define IVP_DOPRI5_STAGE_BODY(ODE) \
+{ const double cA21 = KC(A21);                                                                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h * cA21, k1[i]);                                                              \
+}                                                                                                                                   \
+    ODE(x + KC(C2) * h, y1, k2);                                                                                                    \
+{ const double cA31 = KC(A31), cA32 = KC(A32);                                                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA31, k1[i], cA32, k2[i]));                                          \
+}                                                                                                                                   \
+    ODE(x + KC(C3) * h, y1, k3);                                                                                                    \
+{ const double cA41 = KC(A41), cA42 = KC(A42), cA43 = KC(A43);                                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA41, k1[i], cA42, k2[i], cA43, k3[i]));                             \
+}                                                                                                                                   \
+    ODE(x + KC(C4) * h, y1, k4);                                                                                                    \
+{ const double cA51 = KC(A51), cA52 = KC(A52), cA53 = KC(A53), cA54 = KC(A54);                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA51, k1[i], cA52, k2[i], cA53, k3[i], cA54, k4[i]));                \
+}                                                                                                                                   \
+    ODE(x + KC(C5) * h, y1, k5);                                                                                                    \
+{ const double cA61 = KC(A61), cA62 = KC(A62), cA63 = KC(A63), cA64 = KC(A64), cA65 = KC(A65);                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA61, k1[i], cA62, k2[i], cA63, k3[i], cA64, k4[i], cA65, k5[i]));   \
+}                                                                                                                                   \
+    xph = x + h;                                                                                                                    \
+    ODE(xph, y1, k6);                                                                                                               \
+{ const double cA71 = KC(A71), cA73 = KC(A73), cA74 = KC(A74), cA75 = KC(A75), cA76 = KC(A76);                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA71, k1[i], cA73, k3[i], cA74, k4[i], cA75, k5[i], cA76, k6[i]));   \
+}                                                                                                                                   \
+    ODE(xph, y1, k2);   /* k7 -> k2 (FSAL) */                                                                                      
+
+// The stage block of a DOPRI5 attempt: k2 (the FSAL stage k7), k3 .. k6 and the new solution y1 from x, h, y, k1.  It reads
+// nothing else and writes nothing else, so an attempt may run it twice (deferred guard: INB = true on the in-band helpers,
+// folding the operand ranges into acc; INB = false on the plain operators).
+template <class R, bool INB, class ACC>
+IVP_HD void dopri5_stages(double x, double h, double &xph, const double *y, const double *k1, const double *p, uint64_t kz,
+                          double (&k2)[R::N], double (&k3)[R::N], double (&k4)[R::N], double (&k5)[R::N], double (&k6)[R::N],
+                          double (&y1)[R::N], ACC &acc)
+{
+    KC_SCOPE_FROM(kz)
+    constexpr int N = R::N;
+    using namespace dopri5_tab;
+#define IVP_STAGE_ODE(t, yin, kout) stage_ode<R, INB>(t, yin, kout, p, acc)
+    IVP_DOPRI5_STAGE_BODY(IVP_STAGE_ODE)
+#undef IVP_STAGE_ODE
+}
+
+// Runs a stage block under the deferred guard (see IvpInbandAcc): on the in-band helpers first, unless an earlier attempt
+// of this chunk already had to be redone; then one wave-wide decision; the plain operators if any lane was out of band.
+// (A macro, not a function taking the block as a callable: every piece must stay force-inlined into the attempt.  Names of
+// the enclosing scope: L, R.  The result does not depend on L.inb_plain being uniform -- the plain pass is always valid.)
+#define IVP_STAGE_BLOCK_DEFERRED(fn, ...)                                                 \
+    {                                                                                     \
+        bool plain = ivp_wave_flag(L.inb_plain);                                          \
+        if (!plain) {                                                                     \
+            IvpInbandAcc acc = ivp_inband_begin(L.inb_seed);                              \
+            fn<R, true>(__VA_ARGS__, acc);                                                \
+            if (!ivp_wave_all(ivp_inband_ok(acc))) { plain = true; L.inb_plain = true; }  \
+        }                                                                                 \
+        if (plain) { IvpNoAcc none; fn<R, false>(__VA_ARGS__, none); }                    \
+    }
+#define IVP_ODE_AS_IS(t, yin, kout) R::ode(t, yin, kout, p)
+// The lean DOPRI5 kernel with the whole DefaultSolOut (FULL = 1: 5 N dense coefficients on top of the stages) sits at 247 of
+// 256 VGPRs with the guard per call and spills 58 of them to scratch with a second stage block: it keeps the guard per
+// call.  The host build defers everywhere, so that tests/helpers/inband_redo_main.cpp covers every flavour.
+#if defined(__HIP_DEVICE_COMPILE__) && !IVP_HOIST
+#define IVP_DEFER_GUARD(M, FULL) (HasInbandOde<R>::v && !((M) == M_DOPRI5 && (FULL) == 1))
+#else
+#define IVP_DEFER_GUARD(M, FULL) (HasInbandOde<R>::v)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // DOPRI5 attempt (dopri5.rs:266-461).  Returns false when the trajectory retired.
 // ------------------------------------------------------------------------------------------------
@@ -1706,16 +1953,7 @@ IVP_HD bool dopri5_attempt(const IvpKArgs &a, uint32_t j, Lane<R::N, R::P> &L)
 {
     KC_SCOPE_KZ(L.kz)
     constexpr int N = R::N;
-    // tableau, dopri5.rs:482-520
-    constexpr double C2 = 0.2, C3 = 0.3, C4 = 0.8, C5 = 8.0 / 9.0;
-    constexpr double A21 = 0.2, A31 = 3.0 / 40.0, A32 = 9.0 / 40.0;
-    constexpr double A41 = 44.0 / 45.0, A42 = -56.0 / 15.0, A43 = 32.0 / 9.0;
-    constexpr double A51 = 19372.0 / 6561.0, A52 = -25360.0 / 2187.0, A53 = 64448.0 / 6561.0, A54 = -212.0 / 729.0;
-    constexpr double A61 = 9017.0 / 3168.0, A62 = -355.0 / 33.0, A63 = 46732.0 / 5247.0, A64 = 49.0 / 176.0, A65 = -5103.0 / 18656.0;
-    constexpr double A71 = 35.0 / 384.0, A73 = 500.0 / 1113.0, A74 = 125.0 / 192.0, A75 = -2187.0 / 6784.0, A76 = 11.0 / 84.0;
-    constexpr double E1 = 71.0 / 57600.0, E3 = -71.0 / 16695.0, E4 = 71.0 / 1920.0, E5 = -17253.0 / 339200.0, E6 = 22.0 / 525.0, E7 = -1.0 / 40.0;
-    constexpr double D1 = -12715105075.0 / 11282082432.0, D3 = 87487479700.0 / 32700410799.0, D4 = -10690763975.0 / 1880347072.0,
-                     D5 = 701980252875.0 / 199316789632.0, D6 = -1453857185.0 / 822651844.0, D7 = 69997945.0 / 29380423.0;
+    using namespace dopri5_tab;
     // struct defaults (dopri5.rs:34-72); solve_ivp overrides only max_step/first_step/max_steps
     constexpr double d_uround = 2.3e-16, d_safety = 0.9, d_beta = 0.04;
     constexpr double d_facc1 = 1.0 / 0.2, d_facc2 = 1.0 / 10.0;
@@ -1731,37 +1969,12 @@ IVP_HD bool dopri5_attempt(const IvpKArgs &a, uint32_t j, Lane<R::N, R::P> &L)
 
     const double *y = L.y, *k1 = L.k1, *p = L.p;
     double k2[N], k3[N], k4[N], k5[N], k6[N], y1[N];
-{ const double cA21 = KC(A21);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h * cA21, k1[i]);
-}
-    R::ode(x + KC(C2) * h, y1, k2, p);
-{ const double cA31 = KC(A31), cA32 = KC(A32);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA31, k1[i], cA32, k2[i]));
-}
-    R::ode(x + KC(C3) * h, y1, k3, p);
-{ const double cA41 = KC(A41), cA42 = KC(A42), cA43 = KC(A43);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA41, k1[i], cA42, k2[i], cA43, k3[i]));
-}
-    R::ode(x + KC(C4) * h, y1, k4, p);
-{ const double cA51 = KC(A51), cA52 = KC(A52), cA53 = KC(A53), cA54 = KC(A54);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA51, k1[i], cA52, k2[i], cA53, k3[i], cA54, k4[i]));
-}
-    R::ode(x + KC(C5) * h, y1, k5, p);
-{ const double cA61 = KC(A61), cA62 = KC(A62), cA63 = KC(A63), cA64 = KC(A64), cA65 = KC(A65);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA61, k1[i], cA62, k2[i], cA63, k3[i], cA64, k4[i], cA65, k5[i]));
-}
-    const double xph = x + h;
-    R::ode(xph, y1, k6, p);
-{ const double cA71 = KC(A71), cA73 = KC(A73), cA74 = KC(A74), cA75 = KC(A75), cA76 = KC(A76);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA71, k1[i], cA73, k3[i], cA74, k4[i], cA75, k5[i], cA76, k6[i]));
-}
-    R::ode(xph, y1, k2, p);  // k7 -> k2 (FSAL)
+    double xph;
+    if constexpr (IVP_DEFER_GUARD(M_DOPRI5, FULL)) {
+        IVP_STAGE_BLOCK_DEFERRED(dopri5_stages, x, h, xph, y, k1, p, IVP_KZ_CUR, k2, k3, k4, k5, k6, y1)
+    } else {
+        IVP_DOPRI5_STAGE_BODY(IVP_ODE_AS_IS)
+    }
     L.d_nfev += 6;
 
     double cont[FULL == 1 ? 5 * N : 1];
@@ -2057,6 +2270,87 @@ IVP_HD void dop853_sample_body(const IvpKArgs &a, uint32_t j, uint32_t kd)
     }
 }
 
+// The statements of the DOP853 stage block, like IVP_DOPRI5_STAGE_BODY (k2 .. k10, y1).
+#define IVP_DOP853_STAGE_BODY(ODE) \
+{ const double cA21 = KC(A21);                                                                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h * cA21, k1[i]);                                                                                                                 \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C2) * h, y1, k2);                                                                                                                                                       \
+{ const double cA31 = KC(A31), cA32 = KC(A32);                                                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA31, k1[i], cA32, k2[i]));                                                                                             \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C3) * h, y1, k3);                                                                                                                                                       \
+{ const double cA41 = KC(A41), cA43 = KC(A43);                                                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA41, k1[i], cA43, k3[i]));                                                                                             \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C4) * h, y1, k4);                                                                                                                                                       \
+{ const double cA51 = KC(A51), cA53 = KC(A53), cA54 = KC(A54);                                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA51, k1[i], cA53, k3[i], cA54, k4[i]));                                                                                \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C5) * h, y1, k5);                                                                                                                                                       \
+{ const double cA61 = KC(A61), cA64 = KC(A64), cA65 = KC(A65);                                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA61, k1[i], cA64, k4[i], cA65, k5[i]));                                                                                \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C6) * h, y1, k6);                                                                                                                                                       \
+{ const double cA71 = KC(A71), cA74 = KC(A74), cA75 = KC(A75), cA76 = KC(A76);                                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA71, k1[i], cA74, k4[i], cA75, k5[i], cA76, k6[i]));                                                                   \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C7) * h, y1, k7);                                                                                                                                                       \
+{ const double cA81 = KC(A81), cA84 = KC(A84), cA85 = KC(A85), cA86 = KC(A86), cA87 = KC(A87);                                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA81, k1[i], cA84, k4[i], cA85, k5[i], cA86, k6[i], cA87, k7[i]));                                                      \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C8) * h, y1, k8);                                                                                                                                                       \
+{ const double cA91 = KC(A91), cA94 = KC(A94), cA95 = KC(A95), cA96 = KC(A96), cA97 = KC(A97), cA98 = KC(A98);                                                                         \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i)                                                                                                                                                        \
+        y1[i] = IVP_MA(y[i], h, IVP_LC(cA91, k1[i], cA94, k4[i], cA95, k5[i], cA96, k6[i], cA97, k7[i], cA98, k8[i]));                                                                 \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C9) * h, y1, k9);                                                                                                                                                       \
+{ const double cA101 = KC(A101), cA104 = KC(A104), cA105 = KC(A105), cA106 = KC(A106), cA107 = KC(A107), cA108 = KC(A108), cA109 = KC(A109);                                           \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i)                                                                                                                                                        \
+        y1[i] = IVP_MA(y[i], h, IVP_LC(cA101, k1[i], cA104, k4[i], cA105, k5[i], cA106, k6[i], cA107, k7[i], cA108, k8[i], cA109, k9[i]));                                             \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C10) * h, y1, k10);                                                                                                                                                     \
+{ const double cA111 = KC(A111), cA114 = KC(A114), cA115 = KC(A115), cA116 = KC(A116), cA117 = KC(A117), cA118 = KC(A118), cA119 = KC(A119), cA1110 = KC(A1110);                       \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i)                                                                                                                                                        \
+        y1[i] = IVP_MA(y[i], h, IVP_LC(cA111, k1[i], cA114, k4[i], cA115, k5[i], cA116, k6[i], cA117, k7[i], cA118, k8[i], cA119, k9[i], cA1110, k10[i]));                             \
+}                                                                                                                                                                                      \
+    ODE(x + KC(C11) * h, y1, k2);                                                                                                                                                      \
+    xph = x + h;                                                                                                                                                                       \
+{ const double cA121 = KC(A121), cA124 = KC(A124), cA125 = KC(A125), cA126 = KC(A126), cA127 = KC(A127), cA128 = KC(A128), cA129 = KC(A129), cA1210 = KC(A1210), cA1211 = KC(A1211);   \
+    _Pragma("unroll")                                                                                                                                                                  \
+    for (int i = 0; i < N; ++i)                                                                                                                                                        \
+        y1[i] = IVP_MA(y[i], h, IVP_LC(cA121, k1[i], cA124, k4[i], cA125, k5[i], cA126, k6[i], cA127, k7[i], cA128, k8[i], cA129, k9[i],                                               \
+                                       cA1210, k10[i], cA1211, k2[i]));                                                                                                                \
+}                                                                                                                                                                                      \
+    ODE(xph, y1, k3);                                                                                                                                                                 
+
+// The stage block of a DOP853 attempt: the eleven stages behind k1 (derivatives in k2 .. k10, k4 and k5 free for the
+// attempt's combinations afterwards) and the last stage's argument y1, from x, h, y, k1.  Like dopri5_stages it reads and
+// writes nothing else, so the deferred guard may run it twice.  The new derivative of an accepted step and the three
+// dense-output stages come after the attempt's first writes and keep R::ode with its guard per call.
+template <class R, bool INB, class ACC>
+IVP_HD void dop853_stages(double x, double h, double &xph, const double *y, const double *k1, const double *p, uint64_t kz,
+                          double (&k2)[R::N], double (&k3)[R::N], double (&k4)[R::N], double (&k5)[R::N], double (&k6)[R::N],
+                          double (&k7)[R::N], double (&k8)[R::N], double (&k9)[R::N], double (&k10)[R::N], double (&y1)[R::N], ACC &acc)
+{
+    KC_SCOPE_FROM(kz)
+    constexpr int N = R::N;
+    using namespace dop853_tab;
+#define IVP_STAGE_ODE(t, yin, kout) stage_ode<R, INB>(t, yin, kout, p, acc)
+    IVP_DOP853_STAGE_BODY(IVP_STAGE_ODE)
+#undef IVP_STAGE_ODE
+}
+
 // ------------------------------------------------------------------------------------------------
 // DOP853 attempt (dop853.rs:272-653)
 // ------------------------------------------------------------------------------------------------
@@ -2081,67 +2375,12 @@ IVP_HD bool dop853_attempt(const IvpKArgs &a, uint32_t j, Lane<R::N, R::P> &L)
 
     const double *y = L.y, *k1 = L.k1, *p = L.p;
     double k2[N], k3[N], k4[N], k5[N], k6[N], k7[N], k8[N], k9[N], k10[N], y1[N];
-{ const double cA21 = KC(A21);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h * cA21, k1[i]);
-}
-    R::ode(x + KC(C2) * h, y1, k2, p);
-{ const double cA31 = KC(A31), cA32 = KC(A32);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA31, k1[i], cA32, k2[i]));
-}
-    R::ode(x + KC(C3) * h, y1, k3, p);
-{ const double cA41 = KC(A41), cA43 = KC(A43);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA41, k1[i], cA43, k3[i]));
-}
-    R::ode(x + KC(C4) * h, y1, k4, p);
-{ const double cA51 = KC(A51), cA53 = KC(A53), cA54 = KC(A54);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA51, k1[i], cA53, k3[i], cA54, k4[i]));
-}
-    R::ode(x + KC(C5) * h, y1, k5, p);
-{ const double cA61 = KC(A61), cA64 = KC(A64), cA65 = KC(A65);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA61, k1[i], cA64, k4[i], cA65, k5[i]));
-}
-    R::ode(x + KC(C6) * h, y1, k6, p);
-{ const double cA71 = KC(A71), cA74 = KC(A74), cA75 = KC(A75), cA76 = KC(A76);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA71, k1[i], cA74, k4[i], cA75, k5[i], cA76, k6[i]));
-}
-    R::ode(x + KC(C7) * h, y1, k7, p);
-{ const double cA81 = KC(A81), cA84 = KC(A84), cA85 = KC(A85), cA86 = KC(A86), cA87 = KC(A87);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y1[i] = IVP_MA(y[i], h, IVP_LC(cA81, k1[i], cA84, k4[i], cA85, k5[i], cA86, k6[i], cA87, k7[i]));
-}
-    R::ode(x + KC(C8) * h, y1, k8, p);
-{ const double cA91 = KC(A91), cA94 = KC(A94), cA95 = KC(A95), cA96 = KC(A96), cA97 = KC(A97), cA98 = KC(A98);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        y1[i] = IVP_MA(y[i], h, IVP_LC(cA91, k1[i], cA94, k4[i], cA95, k5[i], cA96, k6[i], cA97, k7[i], cA98, k8[i]));
-}
-    R::ode(x + KC(C9) * h, y1, k9, p);
-{ const double cA101 = KC(A101), cA104 = KC(A104), cA105 = KC(A105), cA106 = KC(A106), cA107 = KC(A107), cA108 = KC(A108), cA109 = KC(A109);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        y1[i] = IVP_MA(y[i], h, IVP_LC(cA101, k1[i], cA104, k4[i], cA105, k5[i], cA106, k6[i], cA107, k7[i], cA108, k8[i], cA109, k9[i]));
-}
-    R::ode(x + KC(C10) * h, y1, k10, p);
-{ const double cA111 = KC(A111), cA114 = KC(A114), cA115 = KC(A115), cA116 = KC(A116), cA117 = KC(A117), cA118 = KC(A118), cA119 = KC(A119), cA1110 = KC(A1110);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        y1[i] = IVP_MA(y[i], h, IVP_LC(cA111, k1[i], cA114, k4[i], cA115, k5[i], cA116, k6[i], cA117, k7[i], cA118, k8[i], cA119, k9[i], cA1110, k10[i]));
-}
-    R::ode(x + KC(C11) * h, y1, k2, p);
-    const double xph = x + h;
-{ const double cA121 = KC(A121), cA124 = KC(A124), cA125 = KC(A125), cA126 = KC(A126), cA127 = KC(A127), cA128 = KC(A128), cA129 = KC(A129), cA1210 = KC(A1210), cA1211 = KC(A1211);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        y1[i] = IVP_MA(y[i], h, IVP_LC(cA121, k1[i], cA124, k4[i], cA125, k5[i], cA126, k6[i], cA127, k7[i], cA128, k8[i], cA129, k9[i],
-                                       cA1210, k10[i], cA1211, k2[i]));
-}
-    R::ode(xph, y1, k3, p);
+    double xph;
+    if constexpr (IVP_DEFER_GUARD(M_DOP853, FULL)) {
+        IVP_STAGE_BLOCK_DEFERRED(dop853_stages, x, h, xph, y, k1, p, IVP_KZ_CUR, k2, k3, k4, k5, k6, k7, k8, k9, k10, y1)
+    } else {
+        IVP_DOP853_STAGE_BODY(IVP_ODE_AS_IS)
+    }
     L.d_nfev += 11;
 
 { const double cB1 = KC(B1), cB6 = KC(B6), cB7 = KC(B7), cB8 = KC(B8), cB9 = KC(B9), cB10 = KC(B10), cB11 = KC(B11), cB12 = KC(B12);
@@ -2439,6 +2678,7 @@ IVP_HD uint32_t chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out)
 #endif
     if (a.has_max_step) L.hmax = (M == M_DOPRI5) ? a.max_step : fabs(a.max_step);
     else L.hmax = fabs(L.xend - L.x0);
+    if constexpr (HasInbandOde<R>::v) { L.inb_seed = R::inband_seed(L.p); L.inb_plain = false; }
     uint32_t it = 0;
     bool run = true;
     while (run && it < a.chunk) {
