@@ -65,6 +65,7 @@ typedef enum {
     IVP_ERR_TOLERANCE_SIZE_MISMATCH = -4, /* ConfigError::ToleranceSizeMismatch (a panic in the reference, src/methods/mod.rs:156-161) */
     IVP_ERR_INVALID_STEP_SIZE = -5,       /* ConfigError::InvalidStepSize (RK4: first_step zero / wrong sign, rk4.rs:81-87) */
     IVP_ERR_INVALID_SCALE_FACTORS = -6,   /* ConfigError::InvalidScaleFactors  */
+    IVP_ERR_INVALID_DAE_PARTITION = -7,   /* ConfigError::InvalidDAEPartition (ivp_radau_solve_dae*: nind1 + nind2 + nind3 != n) */
     IVP_ERR_BAD_ARGUMENT = -100,          /* NULL pointer, unknown rhs id, n mismatch ...            */
     IVP_ERR_UNSUPPORTED_METHOD = -101,    /* RADAU as ivp_options_t.method: solve_ivp() does not route to it yet (ivp_radau_solve*() is the way in) */
     IVP_ERR_NO_DEVICE = -102,             /* no HIP device: there is deliberately no CPU fallback    */
@@ -347,8 +348,23 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  * Errors, reported before the device is touched: the ConfigErrors of radau.rs:132-262 (MUST_BE_POSITIVE: newton_maxiter;
  * OUT_OF_RANGE: uround, safety_factor, newton_maxiter > 15; INVALID_SCALE_FACTORS; INVALID_STEP_SIZE: first_step == 0;
  * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 8, problems
- * with event functions, fp_mode = FMA and variant = 3.  Mass matrices, DAE index sets, banded storage and the CSR
- * one-pass / dense / events / multi-device forms are not on this path yet.
+ * with event functions, fp_mode = FMA and variant = 3.  Banded storage and the CSR one-pass / dense / events /
+ * multi-device forms are not on this path yet.
+ *
+ * M y' = f(t, y) with a constant, possibly singular mass matrix and index-1/2/3 algebraic variables: ivp_radau_solve_dae*()
+ * and ivp_radau_dae_check(), the three calls above plus `dae`.  The mass matrix comes from the problem -- a hiprtc snippet
+ * compiled with IVP_RHS_HAS_MASS (below) -- and is evaluated once per trajectory, as the reference calls f.mass() once
+ * (radau.rs:358-359); a problem without the hook is solved with the identity, and gives what ivp_radau_solve*() gives.
+ * ivp_radau_dae_t is the reference's nind1 / nind2 / nind3 (Option<usize> each: has_x = 0 means None), validated by its rules
+ * in its order (radau.rs:210-246): none given -- nind1 = n (a pure ODE partition; dae == NULL means the same); nind1 omitted
+ * -- inferred as n - nind2 - nind3, IVP_ERR_INVALID_DAE_PARTITION if nind2 + nind3 > n; else the three must sum to n.  A
+ * negative count (not expressible in the reference) gets the same error.  Variables are ordered index-1 first, then
+ * index-2, then index-3; the error scale of an index-2 (index-3) variable is divided by the step ratio hhfac (hhfac^2)
+ * on every attempt (radau.rs:435-444).  nind2 + nind3 > 0 for a problem WITHOUT the mass hook is IVP_ERR_BAD_ARGUMENT
+ * ("not yet").  The refusals above (n > 8, events, FMA, variant = 3) apply unchanged.
+ * Deliberate deviation: a problem compiled with IVP_RHS_HAS_MASS is refused (IVP_ERR_BAD_ARGUMENT) by every other entry
+ * point, ivp_radau_solve*() included -- the reference's explicit methods and BDF ignore IVP::mass silently, which solves a
+ * different equation without saying so.
  */
 typedef struct {
     double uround;          /* 2.3e-16 */
@@ -361,6 +377,13 @@ typedef struct {
     int32_t predictive;     /* 1: Gustafsson controller */
     int32_t reserved;       /* 0 */
 } ivp_radau_settings_t;
+
+typedef struct {
+    int32_t has_nind1, nind1;   /* index-1 variables (default: all) */
+    int32_t has_nind2, nind2;   /* index-2 variables (default: 0)   */
+    int32_t has_nind3, nind3;   /* index-3 variables (default: 0)   */
+    int32_t reserved[2];        /* 0 */
+} ivp_radau_dae_t;
 
 void ivp_radau_settings_default(ivp_radau_settings_t *settings);
 /* The validation of ivp_batch_solve*() (ivp_options_check) and of ivp_radau_solve*() (ivp_radau_check) on its own: no
@@ -375,6 +398,15 @@ int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const d
 int ivp_radau_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
                            const ivp_radau_settings_t *settings, ivp_batch_result_t *out, void *hip_stream);
+int ivp_radau_dae_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                        const ivp_radau_dae_t *dae, char *message, size_t message_len);
+int ivp_radau_solve_dae(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                        const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                        const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out);
+int ivp_radau_solve_dae_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                               const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                               const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                               void *hip_stream);
 
 /*
  * Solution.t / Solution.y of B solve_ivp() calls in ONE call and ONE integration (ABI v5).
@@ -650,8 +682,15 @@ int ivp_step_log_fetch_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_pr
  *     __device__ void jac_col(int col, double x, const double* y, double* column, const double* p);
  * Either way the storage starts zeroed and persists between calls like the reference's Matrix (bdf.rs:152): entries an
  * override never writes are 0.
+ * flags & IVP_RHS_HAS_MASS (ivp_rhs_compile_ex only, n <= 8, not with IVP_RHS_BANDED) -- the snippet also defines the
+ * trait's constant mass matrix (src/ivp.rs:111-120), row-major m[row*n + col]:
+ *     __device__ void mass(double* m, const double* p);
+ * m starts zeroed (entries the hook never writes are 0, like the reference's full Matrix); p holds the trajectory's
+ * parameters, so M may differ per trajectory.  Read by ivp_radau_solve_dae*() only; every other entry point refuses such a
+ * problem (see there).
  */
 #define IVP_RHS_HAS_JAC 1u
+#define IVP_RHS_HAS_MASS 4u
 int ivp_rhs_compile(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_t n_params, void **handle);
 int ivp_rhs_compile_events(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, void **handle);
 int ivp_rhs_compile_ex(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags, void **handle);

@@ -98,6 +98,14 @@ class RadauSettingsT(C.Structure):
     ]
 
 
+class RadauDaeT(C.Structure):
+    """``ivp_radau_dae_t``: nind1 / nind2 / nind3 of the RADAU struct (``has_x = 0`` is ``None``)."""
+    _fields_ = [
+        ("has_nind1", C.c_int32), ("nind1", C.c_int32), ("has_nind2", C.c_int32), ("nind2", C.c_int32),
+        ("has_nind3", C.c_int32), ("nind3", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
 # every symbol include/ivp_hip.h declares
 EXPORTS = (
     "ivp_abi_version", "ivp_device_count", "ivp_ctx_create", "ivp_ctx_destroy", "ivp_last_error_string",
@@ -109,11 +117,13 @@ EXPORTS = (
     "ivp_batch_solve_dense_device", "ivp_batch_solve_dense", "ivp_dense_log_fetch_device", "ivp_dense_log_free", "ivp_dense_eval_device",
     "ivp_batch_solve_events_device", "ivp_batch_solve_events", "ivp_event_log_fetch_device", "ivp_event_log_free",
     "ivp_radau_settings_default", "ivp_radau_solve", "ivp_radau_solve_device", "ivp_options_check", "ivp_radau_check",
+    "ivp_radau_dae_check", "ivp_radau_solve_dae", "ivp_radau_solve_dae_device",
 )
 
 ERRORS = {
     0: "IVP_OK", -1: "IVP_ERR_MUST_BE_POSITIVE", -2: "IVP_ERR_OUT_OF_RANGE", -3: "IVP_ERR_NEGATIVE_TOLERANCE",
     -4: "IVP_ERR_TOLERANCE_SIZE_MISMATCH", -5: "IVP_ERR_INVALID_STEP_SIZE", -6: "IVP_ERR_INVALID_SCALE_FACTORS",
+    -7: "IVP_ERR_INVALID_DAE_PARTITION",
     -100: "IVP_ERR_BAD_ARGUMENT", -101: "IVP_ERR_UNSUPPORTED_METHOD", -102: "IVP_ERR_NO_DEVICE",
     -103: "IVP_ERR_HIP", -104: "IVP_ERR_JIT", -105: "IVP_ERR_LOG_CAPACITY",
 }
@@ -186,6 +196,13 @@ def load():
     L.ivp_radau_solve.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1]]
     L.ivp_radau_solve_device.restype = C.c_int
     L.ivp_radau_solve_device.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1], C.c_void_p]
+    L.ivp_radau_dae_check.restype = C.c_int
+    L.ivp_radau_dae_check.argtypes = [C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT), C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT),
+                                      C.c_char_p, C.c_size_t]
+    L.ivp_radau_solve_dae.restype = C.c_int
+    L.ivp_radau_solve_dae.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT), solve_args[-1]]
+    L.ivp_radau_solve_dae_device.restype = C.c_int
+    L.ivp_radau_solve_dae_device.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT), solve_args[-1], C.c_void_p]
     L.ivp_batch_solve_multi.argtypes = [C.POINTER(ShardT), C.c_int32, C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT),
                                         C.c_int32, C.POINTER(BatchResultT)]
     L.ivp_batch_solve_multi_host.restype = C.c_int

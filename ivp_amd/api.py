@@ -304,7 +304,8 @@ class DeviceIVP(IVP):
     rhs_id = 1000
 
     def __init__(self, source: str, n: int, params: Sequence[float] = (), ctx: "Context" = None,
-                 events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None, jac_storage: str = "full"):
+                 events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None, jac_storage: str = "full", *,
+                 mass: bool = False):
         """``events``: one EventConfig per event function; ``source`` must then also define
         ``__device__ void events(double x, const double* y, double* g, const double* p)``.
         ``jac=True``: ``source`` also overrides the trait's Jacobian (src/ivp.rs:67-107), used by BDF in place of the
@@ -321,13 +322,24 @@ class DeviceIVP(IVP):
         ``jac_storage="banded"`` (needs a pattern, not with ``jac=True``; the reference's ``MatrixStorage::Banded{ml, mu}``):
         BDF stores J and the factors of (I - cJ) by bands, with the bandwidths of the pattern (``jac_bandwidth``), and
         factorises and solves with the banded kernels -- same results bit for bit, (3 ml + 2 mu + 2) n doubles per
-        trajectory instead of 2 n^2 (``jac_layout``).  The default ``"full"`` is the n x n storage."""
+        trajectory instead of 2 n^2 (``jac_layout``).  The default ``"full"`` is the n x n storage.
+        ``mass=True`` (n <= 8, not with ``jac_sparsity`` or ``jac_storage="banded"``): ``source`` also defines the trait's constant mass matrix
+        (src/ivp.rs:111-120), ``__device__ void mass(double* m, const double* p)`` with ``m[row * n + col]``, zeroed on
+        entry, evaluated once per trajectory with its parameters.  Such a problem is solved by ``ivp_amd.Radau`` only
+        (``M y' = f``, index-1/2/3 DAEs); every other solver refuses it instead of ignoring M."""
         if jac_storage not in ("full", "banded"):
             raise ValueError(f'jac_storage must be "full" or "banded", got {jac_storage!r}')
         if jac_storage == "banded" and jac_sparsity is None:
             raise ValueError('jac_storage="banded" needs a jac_sparsity pattern: the bandwidths are taken from it')
         if jac_storage == "banded" and jac:
             raise ValueError('jac_storage="banded" with jac=True: an analytic jac_col in band storage is not supported')
+        if mass and jac_storage == "banded":
+            raise ValueError('mass=True with jac_storage="banded": banded storage is BDF\'s, the mass matrix is Radau\'s')
+        if mass and int(n) > 8:
+            raise ValueError("mass=True needs n <= 8: the mass matrix is read by the Radau DAE call only")
+        if mass and jac_sparsity is not None:
+            raise ValueError("mass=True with jac_sparsity: a pattern is read by BDF on 8 < n <= 512, the mass matrix by Radau on n <= 8")
+        self.has_mass = bool(mass)
         self.source = source
         self.n = int(n)
         self._params = tuple(float(v) for v in params)
@@ -341,17 +353,18 @@ class DeviceIVP(IVP):
         # process (a few hundred bytes of host state plus the loaded code objects).
         pattern = None if jac_sparsity is None else sparsity_csc(jac_sparsity, self.n)
         key = (source, self.n, self.n_params, len(self._events), bool(jac),
-               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()), jac_storage)
+               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()), jac_storage, bool(mass))
         h = _rhs_records.get(key)
         if h is None:
             h = C.c_void_p()
             if pattern is None:
                 rc = self._ctx.lib.ivp_rhs_compile_ex(self._ctx.handle, source.encode(), self.n, self.n_params,
-                                                      len(self._events), 1 if jac else 0, C.byref(h))
+                                                      len(self._events), (1 if jac else 0) | (RHS_HAS_MASS if mass else 0), C.byref(h))
             else:
                 i32p = C.POINTER(C.c_int32)
                 rc = self._ctx.lib.ivp_rhs_compile_sparse(self._ctx.handle, source.encode(), self.n, self.n_params,
-                                                          len(self._events), (1 if jac else 0) | (RHS_BANDED if jac_storage == "banded" else 0),
+                                                          len(self._events),
+                                                          (1 if jac else 0) | (RHS_BANDED if jac_storage == "banded" else 0) | (RHS_HAS_MASS if mass else 0),
                                                           pattern[0].ctypes.data_as(i32p),
                                                           pattern[1].ctypes.data_as(i32p), C.byref(h))
             if rc != 0:
@@ -382,7 +395,8 @@ class DeviceIVP(IVP):
 
 
 RHS_BANDED = 2   # IVP_RHS_BANDED (include/ivp_hip.h)
-_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern, jac_storage) -> ivp_rhs_compile_ex / _sparse handle
+RHS_HAS_MASS = 4   # IVP_RHS_HAS_MASS
+_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern, jac_storage, mass) -> ivp_rhs_compile_ex / _sparse handle
 
 
 def sparsity_csc(jac_sparsity, n: int):
@@ -894,7 +908,7 @@ class PendingBatch:
 
 
 def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None, _radau=None):
+                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None, _radau=None, _radau_dae=None):
     """B independent ``solve_ivp(f, t0[b], t1[b], y0[:, b], options)`` calls on the GPU.
 
     ``y0``: ``[n, B]`` float64, numpy (host path: staged through the library) or a CUDA torch tensor
@@ -1103,6 +1117,16 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
                                                    ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_steplog), stream)
         if rc == -105:   # IVP_ERR_LOG_CAPACITY: the integration is complete, the records wait in the pool for larger buffers
             rc = 0
+    elif _radau is not None and _radau_dae is not None:   # M y' = f / DAE index sets (ivp_amd.Radau): a _lib.RadauDaeT
+        dae = _radau_dae
+        if on_device:
+            import torch
+            stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
+            rc = ctx.lib.ivp_radau_solve_dae_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                    ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(dae), C.byref(r), stream)
+        else:
+            rc = ctx.lib.ivp_radau_solve_dae(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                             ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(dae), C.byref(r))
     elif _radau is not None and on_device:
         import torch
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
@@ -1386,7 +1410,7 @@ def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = N
 
 
 def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Options = None,
-              ctx: Context = None, _radau=None) -> Solution:
+              ctx: Context = None, _radau=None, _radau_dae=None) -> Solution:
     """``solve_ivp(&f, x0, xend, &y0, options) -> Result<Solution, Error>`` (solve_ivp.rs:99-108) for
     one trajectory, executed by the GPU kernels (a batch of one).  ``Err(..)`` becomes an exception."""
     options = options or Options()
@@ -1421,7 +1445,7 @@ def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Opti
         pr = np.asarray(f.params(), dtype=np.float64).reshape(f.n_params, 1) if f.n_params else None
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx, _radau=_radau)
+            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx, _radau=_radau, _radau_dae=_radau_dae)
         used = 0
         if r.n_log is not None:
             used = max(used, int(r.n_log[0]))

@@ -80,7 +80,7 @@ void set_active(ivp_ctx *ctx, bool on)
 // (dopri5.rs:143-198, dop853.rs:135-193, rk23.rs:102-129) for the fields solve_ivp() can set, plus
 // the Tolerance length rule (mod.rs:156-161).
 }  // namespace
-int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, bool radau)
+int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, int radau)
 {
     if (!prob || !opt) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null problem/options");
     int n, p;
@@ -98,6 +98,9 @@ int ivp_host::validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const 
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "problem dims (n=%d,p=%d) do not match rhs (n=%d,p=%d)", prob->n, prob->n_params, n, p);
     if (n < 1 || n > IVP_MAX_GROUP_N || p > IVP_MAX_P) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
     if (B == 0 || B > 0x7FFFFFFFull) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "batch size %zu out of range", B);
+    // Deliberate deviation: the reference's explicit methods and BDF ignore IVP::mass, which silently solves another equation
+    if (prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit) && radau != IVP_VALIDATE_RADAU_DAE)
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "the problem has a mass matrix (IVP_RHS_HAS_MASS): it is honoured by the Radau DAE call only (ivp_radau_solve_dae*)");
     if (opt->method == IVP_RADAU && !radau)
         return fail(ctx, IVP_ERR_UNSUPPORTED_METHOD, "method %d (RADAU) is not on the accelerated path of solve_ivp (ivp_radau_solve is the direct call)", opt->method);
     if (opt->method < IVP_RK23 || opt->method > IVP_BDF) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown method %d", opt->method);
@@ -604,9 +607,46 @@ namespace {
 
 // RADAU::solve's input validation (radau.rs:132-262) for the fields of ivp_radau_settings_t / ivp_options_t, after the
 // checks every entry point shares; what the Radau path does not cover yet is IVP_ERR_BAD_ARGUMENT.  No device is touched.
-int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *rad, int *n_out, int *p_out)
+// what the Radau entry points hand down: the public settings, and for ivp_radau_solve_dae*() the resolved DAE partition
+struct RadauCall : ivp_radau_settings_t {
+    int dae_call = 0;                    // ivp_radau_solve_dae*(): a problem with a mass matrix is accepted
+    const ivp_radau_dae_t *dae = nullptr;
+    int nind2 = 0, nind3 = 0;            // set by radau_validate
+    RadauCall(const ivp_radau_settings_t *s, int dae_call_, const ivp_radau_dae_t *dae_) : dae_call(dae_call_), dae(dae_)
+    {
+        if (s) *static_cast<ivp_radau_settings_t *>(this) = *s;
+        else ivp_radau_settings_default(this);
+    }
+};
+
+// the DAE partition, by the reference's rules and in its order (radau.rs:210-246); the counts are usize there, so a negative
+// one cannot be expressed: it gets the same error
+int radau_partition(ivp_ctx *ctx, int n, const ivp_radau_dae_t *dae, int *nind2_out, int *nind3_out)
 {
-    const int rc = validate(ctx, prob, B, opt, n_out, p_out, true);
+    int nind1 = 0, nind2 = 0, nind3 = 0;
+    if (dae) {
+        if ((dae->has_nind1 && dae->nind1 < 0) || (dae->has_nind2 && dae->nind2 < 0) || (dae->has_nind3 && dae->nind3 < 0))
+            return fail(ctx, IVP_ERR_INVALID_DAE_PARTITION, "invalid DAE partition: a negative count");
+        nind1 = dae->has_nind1 ? dae->nind1 : 0;
+        nind2 = dae->has_nind2 ? dae->nind2 : 0;
+        nind3 = dae->has_nind3 ? dae->nind3 : 0;
+    }
+    const bool any = dae && (dae->has_nind1 || dae->has_nind2 || dae->has_nind3);
+    if (!any) nind1 = n;
+    else if (!dae->has_nind1) {
+        if ((int64_t)nind2 + (int64_t)nind3 > n)
+            return fail(ctx, IVP_ERR_INVALID_DAE_PARTITION, "invalid DAE partition: n = %d, nind1 = %d, nind2 = %d, nind3 = %d", n, nind1, nind2, nind3);
+        nind1 = n - nind2 - nind3;
+    } else if ((int64_t)nind1 + (int64_t)nind2 + (int64_t)nind3 != n)
+        return fail(ctx, IVP_ERR_INVALID_DAE_PARTITION, "invalid DAE partition: n = %d, nind1 = %d, nind2 = %d, nind3 = %d", n, nind1, nind2, nind3);
+    *nind2_out = nind2;
+    *nind3_out = nind3;
+    return IVP_OK;
+}
+
+int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, RadauCall *rad, int *n_out, int *p_out)
+{
+    const int rc = validate(ctx, prob, B, opt, n_out, p_out, rad->dae_call ? IVP_VALIDATE_RADAU_DAE : IVP_VALIDATE_RADAU);
     if (rc != IVP_OK) return rc;
     const int n = *n_out;
     if (n > IVP_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_MAX_N);
@@ -620,13 +660,20 @@ int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_
         return fail(ctx, IVP_ERR_INVALID_SCALE_FACTORS, "scale factors min = %g, max = %g", rad->scale_min, rad->scale_max);
     if (rad->newton_maxiter <= 0) return fail(ctx, IVP_ERR_MUST_BE_POSITIVE, "newton_maxiter must be positive");
     if (rad->newton_maxiter > 15) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "newton_maxiter = %d outside [1, 15] (the device's Newton loop is bounded)", rad->newton_maxiter);
+    if (rad->dae_call) {   // radau.rs:210-246 comes before the step size check (:248-261)
+        const int prc = radau_partition(ctx, n, rad->dae, &rad->nind2, &rad->nind3);
+        if (prc != IVP_OK) return prc;
+        // the index-set code exists only in the instantiations with a mass matrix (radau_core.h HasMass)
+        if (rad->nind2 + rad->nind3 > 0 && !(prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit)))
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau index-2 / index-3 variables for a problem without a mass matrix (IVP_RHS_HAS_MASS): not yet");
+    }
     if (opt->has_first_step && opt->first_step == 0.0) return fail(ctx, IVP_ERR_INVALID_STEP_SIZE, "Radau: first_step is zero");
     return IVP_OK;
 }
 
 int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
-                ivp_batch_result_t *out, void *hip_stream, const ivp_radau_settings_t *rad)
+                ivp_batch_result_t *out, void *hip_stream, RadauCall *rad)
 {
     if (!ctx) return IVP_ERR_BAD_ARGUMENT;
     if (ctx->pend.active) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "a solve is already in flight on this context");
@@ -732,6 +779,7 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         a.ctl_facc2 = 1.0 / rad->scale_max;   // facr
         a.ctl_beta = rad->newton_tol;
         a.ctl_nstiff = (uint64_t)rad->newton_maxiter | (rad->has_newton_tol ? 0x100ull : 0ull) | (rad->predictive ? 0x200ull : 0ull);   // IVP_RAD_*
+        a.ctl_nstiff |= ((uint64_t)rad->nind2 << 12) | ((uint64_t)rad->nind3 << 16);   // IVP_RAD_NIND2_SHIFT / IVP_RAD_NIND3_SHIFT (both 0 unless the problem has a mass matrix)
         a.has_ctl = 0;
     }
 
@@ -756,8 +804,10 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         BIND(njev, out->njev, sc_njev, sizeof(uint64_t) * B);
         BIND(nlu, out->nlu, sc_nlu, sizeof(uint64_t) * B);
         // Radau's state lives behind the BDF members of the argument block (ivp_kargs.h), in buffers of its own
-        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * 4 * n * n * B));
-        HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (4 * n + 2) * B));
+        // ... a problem with a mass matrix keeps M behind the four matrices, and scal[n] and hhfac behind cont (radau_core.h)
+        const bool has_mass = prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit);
+        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (has_mass ? 5 : 4) * n * n * B));
+        HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (has_mass ? 5 * n + 3 : 4 * n + 2) * B));
         HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B));
         a.bdf_jac = (double *)ctx->rad_mat.p;
         a.bdf_d = (double *)ctx->rad_cont.p;
@@ -1083,7 +1133,25 @@ int ivp_radau_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *op
         ivp_options_t o = *opt;   // the direct call ignores opt->method and the explicit methods' controller fields
         o.method = IVP_RADAU;
         o.has_settings = 0;
-        rc = radau_validate(&scratch, prob, B, &o, settings ? settings : &dflt, &n, &np);
+        RadauCall call(settings ? settings : &dflt, 0, nullptr);
+        rc = radau_validate(&scratch, prob, B, &o, &call, &n, &np);
+    }
+    copy_message(scratch, message, message_len);
+    return rc;
+}
+
+int ivp_radau_dae_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                        const ivp_radau_dae_t *dae, char *message, size_t message_len)
+{
+    ivp_ctx scratch;
+    int n = 0, np = 0, rc;
+    if (!prob || !opt) rc = fail(&scratch, IVP_ERR_BAD_ARGUMENT, "null problem/options");
+    else {
+        ivp_options_t o = *opt;
+        o.method = IVP_RADAU;
+        o.has_settings = 0;
+        RadauCall call(settings, 1, dae);
+        rc = radau_validate(&scratch, prob, B, &o, &call, &n, &np);
     }
     copy_message(scratch, message, message_len);
     return rc;
@@ -1095,7 +1163,18 @@ int ivp_radau_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
 {
     ivp_radau_settings_t dflt;
     ivp_radau_settings_default(&dflt);
-    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, settings ? settings : &dflt);
+    RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, &call);
+    if (rc != IVP_OK) return rc;
+    return ivp_batch_wait(ctx);
+}
+
+int ivp_radau_solve_dae_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                               const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                               const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out, void *hip_stream)
+{
+    RadauCall call(settings, 1, dae);
+    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, &call);
     if (rc != IVP_OK) return rc;
     return ivp_batch_wait(ctx);
 }
@@ -1239,7 +1318,7 @@ int drive_all(ivp_ctx_t *const *ctxs, const char *live, int n)
 }
 
 int multi_impl(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt,
-               int32_t gather_device, ivp_batch_result_t *gathered, const ivp_radau_settings_t *rad)
+               int32_t gather_device, ivp_batch_result_t *gathered, RadauCall *rad)
 {
     if (!shards || n_shards <= 0 || n_shards > 64) return IVP_ERR_BAD_ARGUMENT;
     DeviceGuard restore_device;   // hipSetDevice below must not leak into the caller (its allocations / launches follow the current device)
@@ -1299,7 +1378,7 @@ int multi_impl(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob,
 
     // ---- gather: shard columns into the batch-wide arrays on gather_device ----
     int n = 0, np = 0;
-    rc = validate(c0, prob, B ? B : 1, opt, &n, &np, rad != nullptr);
+    rc = validate(c0, prob, B ? B : 1, opt, &n, &np, !rad ? IVP_VALIDATE_SOLVE_IVP : rad->dae_call ? IVP_VALIDATE_RADAU_DAE : IVP_VALIDATE_RADAU);
     if (rc != IVP_OK) return rc;
     MemberDesc md[kMembers];
     member_table(result_shape(prob, opt, n), md);
@@ -1368,7 +1447,7 @@ int multi_impl(ivp_shard_t *shards, int32_t n_shards, const ivp_problem_t *prob,
 // the host-pointer solve: stage in, integrate shard by shard, stage out (rad != NULL: the direct Radau call, one context)
 int multi_host_impl(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_problem_t *prob, size_t B, const double *y0,
                     const double *params, const double *t0, size_t t0_len, const double *t1, size_t t1_len,
-                    const ivp_options_t *opt, ivp_batch_result_t *out, const ivp_radau_settings_t *rad)
+                    const ivp_options_t *opt, ivp_batch_result_t *out, RadauCall *rad)
 {
     if (!ctxs || n_ctx <= 0 || n_ctx > 64 || !ctxs[0]) return IVP_ERR_BAD_ARGUMENT;
     ivp_options_t radau_opt;
@@ -1535,7 +1614,17 @@ int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const d
     ivp_radau_settings_t dflt;
     ivp_radau_settings_default(&dflt);
     ivp_ctx_t *one[1] = {ctx};
-    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, settings ? settings : &dflt);
+    RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, &call);
+}
+
+int ivp_radau_solve_dae(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                        const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                        const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out)
+{
+    ivp_ctx_t *one[1] = {ctx};
+    RadauCall call(settings, 1, dae);
+    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, &call);
 }
 
 int ivp_rhs_compile(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_t n_params, void **handle)
@@ -1553,7 +1642,9 @@ int ivp_rhs_compile_ex(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_
     if (!ctx || !ode_source || !handle) return IVP_ERR_BAD_ARGUMENT;
     if (n < 1 || n > IVP_MAX_GROUP_N || n_params < 0 || n_params > IVP_MAX_P || n_events < 0 || n_events > 64)
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
-    if (flags & ~IVP_RHS_HAS_JAC) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if (flags & ~(IVP_RHS_HAS_JAC | IVP_RHS_HAS_MASS)) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if ((flags & IVP_RHS_HAS_MASS) && n > IVP_MAX_N)
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS needs n <= %d: the mass matrix is read by the Radau DAE call only", IVP_MAX_N);
     std::string log;
     int rc = ivp_jit_compile(ctx->device, ode_source, n, n_params, n_events, flags, handle, &log);
     if (rc != IVP_OK) ctx->err = log;

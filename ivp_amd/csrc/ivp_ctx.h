@@ -155,7 +155,9 @@ hipError_t copy_rows_peer(void *dst, int dst_dev, size_t dst_stride, const void 
                           size_t count, size_t rows, hipStream_t s);
 // Options / problem validation shared by every entry point (ivp_capi.cpp)
 // (radau: the call comes from ivp_radau_solve*(), the only entry points that integrate with IVP_RADAU)
-int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, bool radau = false);
+// ... IVP_VALIDATE_RADAU_DAE: ivp_radau_solve_dae*(), the only entry points that accept a problem with a mass matrix)
+enum { IVP_VALIDATE_SOLVE_IVP = 0, IVP_VALIDATE_RADAU = 1, IVP_VALIDATE_RADAU_DAE = 2 };
+int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, int radau = IVP_VALIDATE_SOLVE_IVP);
 // restores the caller's current HIP device when a multi-device entry point returns
 struct DeviceGuard {
     int dev = -1;

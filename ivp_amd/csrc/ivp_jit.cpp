@@ -55,6 +55,7 @@ struct JitModule {
 struct JitRhs {
     int device, n, np, ne;
     bool has_jac = false;   // the snippet defines jac(): IVP::jac override (src/ivp.rs:67-107)
+    bool has_mass = false;  // the snippet defines mass(): IVP::mass (src/ivp.rs:111-120), read by the Radau DAE call only
     std::string ode_source;
     std::string sparsity_source;   // the pattern's tables as device code (empty: no pattern, or the snippet has its own jac_col)
     int n_groups = 0;
@@ -66,6 +67,10 @@ struct JitRhs {
     // loaded, so a handle shared by contexts on several GPUs keeps one module per device
     std::map<std::tuple<int, int, int, int, bool, bool, bool>, JitModule> modules;   // ... , lane-cooperative module, banded factors in LDS
     std::string log;
+    // the code object of the compile-only check of ivp_jit_compile (key: options + source), kept for the first launch that
+    // needs exactly that module: a problem with a mass matrix checks its Radau module, which is also the one it runs
+    std::string checked_key;
+    std::vector<char> checked_code;
 };
 
 std::string join(const char *const *parts)
@@ -161,6 +166,8 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
     const bool radau = method == IVP_RADAU;   // radau_core.h: thread per trajectory, n <= 8, built like rk_radau.hip
     if (group || coop_only || radau) s += "#define IVP_HOIST 2\n";   // a wave that owns its SIMD: coefficients pinned in registers (rk_core.h KC)
     if (radau) s += "#define IVP_MIN_WAVES 1\n";
+    const bool mass = radau && r.has_mass;   // only the Radau modules of a problem with the hook: every other module's source stays what it was
+    if (mass) s += "#define IVP_USER_MASS 1\n";
     s += join(k_src_ivp_kargs_h);
     s += "\n// ---- user right-hand side ----\n";
     s += r.ode_source;
@@ -214,7 +221,9 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                   "#if IVP_USER_JAC\n"
                   "  static IVP_HD void jac(double x, const double* y, double (&j)[N][N], const double* p) { ::jac(x, y, &j[0][0], p); }\n"
                   "#endif\n"
-                  "}; }\n", r.n, r.np);
+                  "%s"
+                  "}; }\n", r.n, r.np,
+                  mass ? "  static IVP_HD void mass(double (&m)[N][N], const double* p) { ::mass(&m[0][0], p); }\n" : "");
     s += buf;
     if (coop_only) {   // eight lanes per trajectory for the tail of a batch: its own module, pinned coefficients
         s += join(k_src_rk_coop_h);
@@ -291,6 +300,13 @@ int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitMo
             }
         }
     }
+    if (out && !r.checked_code.empty() && r.checked_key == opt_key + "\n" + src) {
+        std::vector<char> code;
+        code.swap(r.checked_code);
+        r.checked_key.clear();
+        if (load_module(r, code, out, coop_only) == IVP_OK) return IVP_OK;
+        (void)hipGetLastError();   // fall through and compile
+    }
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "ivp_user_rhs.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
         r.log = "hiprtcCreateProgram failed";
@@ -324,13 +340,17 @@ int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitMo
             if (!o || std::rename(tmp.c_str(), cpath.c_str()) != 0) std::remove(tmp.c_str());
         }
     }
-    if (!out) return IVP_OK;  // compile-only check
+    if (!out) {   // compile-only check
+        if (r.has_mass) { r.checked_key = opt_key + "\n" + src; r.checked_code.swap(code); }
+        return IVP_OK;
+    }
     return load_module(r, code, out, coop_only);
 }
 
 }  // namespace
 
 int ivp_jit_n_events(void *handle) { return handle ? ((JitRhs *)handle)->ne : 0; }
+bool ivp_jit_has_mass(void *handle) { return handle && ((JitRhs *)handle)->has_mass; }
 
 int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log,
                     const int32_t *col_ptr, const int32_t *row_idx)
@@ -367,6 +387,7 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
     r->band_mu = mu;
     r->device = device;
     r->has_jac = (flags & IVP_RHS_HAS_JAC) != 0;
+    r->has_mass = (flags & IVP_RHS_HAS_MASS) != 0;
     r->n = n;
     r->np = n_params;
     r->ne = n_events;
@@ -379,8 +400,10 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
     } else {
         r->arch = "gfx950";
     }
-    // compile the default configuration now so that syntax errors surface at ivp_rhs_compile() time
-    int rc = compile_module(*r, IVP_DOPRI5, IVP_FP_STRICT, n_events > 0, false, nullptr);
+    // compile the default configuration now so that syntax errors surface at ivp_rhs_compile() time -- for a problem with a
+    // mass matrix that is the Radau module, the only one any entry point launches and the only one that instantiates mass()
+    const bool radau_only = r->has_mass && n_events == 0 && n <= IVP_MAX_N;
+    int rc = compile_module(*r, radau_only ? IVP_RADAU : IVP_DOPRI5, IVP_FP_STRICT, n_events > 0, false, nullptr);
     if (rc == IVP_OK && r->has_jac) rc = compile_module(*r, IVP_BDF, IVP_FP_STRICT, n_events > 0, false, nullptr);   // jac() is only instantiated by BDF
     if (rc != IVP_OK) {
         if (log) *log = r->log;

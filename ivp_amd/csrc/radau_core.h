@@ -16,6 +16,13 @@
 // h, hold, h_acc, err_acc, faccon, the flags first / reject / last / call_jac / call_decomp and singular_count.
 // `scal` is recomputed from y (the same two operations on the same operands); theta, dynold and thqold are always
 // written before they are read within one attempt, hhfac is only read for index-2/3 variables (none here).
+//
+// M y' = f with a constant mass matrix and the DAE index sets (radau.rs:358-359, :382-384, :435-444, :525-540, :628-634):
+// a problem functor with a `mass` member (HasMass) gets a fifth persistent matrix, M, written once by the init body and read
+// entry by entry where the identity's 1.0 / 0.0 stand otherwise, and two more pieces of persistent state -- `scal`, which the
+// reference recomputes from y only on acceptance and divides by hhfac (index 2) or hhfac^2 (index 3) on EVERY pass that
+// reaches the Newton iteration, so that the divisions accumulate over rejected attempts, and hhfac itself.  All of it sits
+// behind `if constexpr (HasMass<R>::v)`: a functor without the member compiles to what it compiled to before.
 #pragma once
 
 namespace IVP_NS {
@@ -28,10 +35,13 @@ namespace IVP_NS {
 // ivp_kargs.h ctl_nstiff, as the Radau path fills it: newton_maxiter in the low byte, then two flags
 #define IVP_RAD_HAS_NEWTON_TOL 0x100ull
 #define IVP_RAD_PREDICTIVE 0x200ull
+// ... and, for problems with a mass matrix, the DAE partition: nind2 in bits 12..15, nind3 in bits 16..19 (nind1 = n - nind2 - nind3)
+#define IVP_RAD_NIND2_SHIFT 12
+#define IVP_RAD_NIND3_SHIFT 16
 
 // Radau's view of the shared argument block (ivp_kargs.h: no fields of its own)
-IVP_HD double *radau_mat(const IvpKArgs &a) { return a.bdf_jac; }      // [4 n n][B]  J, E1, E2r, E2i (row-major entries)
-IVP_HD double *radau_cont(const IvpKArgs &a) { return a.bdf_d; }       // [4 n + 2][B] cont, then h_acc, err_acc
+IVP_HD double *radau_mat(const IvpKArgs &a) { return a.bdf_jac; }      // [4 n n][B]  J, E1, E2r, E2i (row-major entries); HasMass: [5 n n][B], then M
+IVP_HD double *radau_cont(const IvpKArgs &a) { return a.bdf_d; }       // [4 n + 2][B] cont, then h_acc, err_acc; HasMass: [5 n + 3][B], then scal[n], hhfac
 IVP_HD double *radau_hold(const IvpKArgs &a) { return a.hlamb; }       // [B]
 IVP_HD uint32_t *radau_piv(const IvpKArgs &a) { return a.bdf_piv; }    // [2][B]      pivot rows of E1 and of E2, 4 bits each
 
@@ -217,7 +227,20 @@ struct RadauK {
 };
 
 // the four persistent matrices of trajectory j: entry e of matrix `which` is radau_mat(a)[(which N N + e) B + j]
-enum { RAD_J = 0, RAD_E1 = 1, RAD_E2R = 2, RAD_E2I = 3 };
+enum { RAD_J = 0, RAD_E1 = 1, RAD_E2R = 2, RAD_E2I = 3, RAD_M = 4 };
+
+// IVP::mass (src/ivp.rs:111-120): a functor that has `static void mass(double (&m)[N][N], const double *p)` -- for hiprtc
+// problems the snippet compiled with IVP_RHS_HAS_MASS defines  __device__ void mass(double* m /* row-major */, const double* p)
+template <class R, class = void>
+struct HasMass { enum { v = 0 }; };
+template <class R>
+struct HasMass<R, decltype((void)&R::mass)> { enum { v = 1 }; };
+// entry e = row N + col of trajectory j's mass matrix: one coalesced load, used for all its products
+template <int N>
+IVP_HD double radau_mass_at(const IvpKArgs &a, uint32_t j, int e)
+{
+    return radau_mat(a)[((size_t)RAD_M * (size_t)(N * N) + (size_t)e) * a.B + j];
+}
 template <int N>
 IVP_HD void radau_mat_load(const IvpKArgs &a, int which, uint32_t j, double (&m)[N][N])
 {
@@ -247,6 +270,18 @@ struct RadauLane {
     uint32_t d_nfev, d_njev, d_nlu, d_nstep, d_naccpt, d_nrejct;
     uint64_t nstep0, naccpt0;
 };
+// ... and what a problem with a mass matrix carries on top of it: the lane state of such a functor is RadauLaneDae, of
+// every other one RadauLane as before (an extra argument, even an empty one, perturbs the register allocation of the
+// kernels without the hook)
+template <int N>
+struct RadauLaneDae : RadauLane<N> {
+    double scal[N], hhfac;
+    int nind1, nind2, nind3;
+};
+template <int N, bool MASS>
+struct RadauLaneSel { typedef RadauLane<N> type; };
+template <int N>
+struct RadauLaneSel<N, true> { typedef RadauLaneDae<N> type; };
 
 // Rust's f64::clamp for min <= max: a NaN passes through
 IVP_HD double radau_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -283,10 +318,25 @@ IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j)
     for (int c = 0; c < N; ++c) { a.y[c * B + j] = y[c]; a.k1[c * B + j] = 0.0; }
 #pragma unroll
     for (int c = 0; c < 4 * N + 2; ++c) radau_cont(a)[(size_t)c * B + j] = 0.0;   // cont, h_acc, err_acc
+    if constexpr (HasMass<R>::v) {
+#pragma unroll
+        for (int c = 4 * N + 2; c < 5 * N + 3; ++c) radau_cont(a)[(size_t)c * B + j] = 0.0;   // scal, hhfac
+    }
     // f.jac() receives a zero-initialised persistent Matrix (radau.rs:282): an override that fills only its non-zero
     // entries leaves zeros elsewhere
 #pragma unroll
     for (int c = 0; c < 4 * N * N; ++c) radau_mat(a)[(size_t)c * B + j] = 0.0;
+    if constexpr (HasMass<R>::v) {
+        // f.mass() is called once, on a zeroed full Matrix (radau.rs:283, :359): entries the hook never writes are 0.  Written
+        // before the early exits below, so the array is always defined.
+        double m[N][N];
+#pragma unroll
+        for (int r = 0; r < N; ++r)
+#pragma unroll
+            for (int c = 0; c < N; ++c) m[r][c] = 0.0;
+        R::mass(m, L.p);
+        radau_mat_store<N>(a, RAD_M, j, m);
+    }
 
     if (fabs(L.xend - L.x0) < 1e-15) {  // solve_ivp.rs:110-145
         if (FULL) {
@@ -333,6 +383,7 @@ IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j)
     a.nfev[j] = 1;
     a.x[j] = L.x0; a.h[j] = h;
     radau_hold(a)[j] = h;
+    if constexpr (HasMass<R>::v) radau_cont(a)[(size_t)(5 * N + 2) * B + j] = h;   // hhfac = h, radau.rs:296
     a.flags[j] = IVP_RAD_FIRST | IVP_RAD_CALLJAC | IVP_RAD_CALLDEC | (L.flags & IVP_F_FIRSTOUT);
     a.status[j] = IVP_RUNNING;
     return IVP_RUNNING;
@@ -340,7 +391,7 @@ IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j)
 
 // One pass of 'main (radau.rs:367-793).  Returns false when the trajectory retired (S.status says how).
 template <class R, int FULL>
-IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lane<R::N, R::P> &L)
+IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, typename RadauLaneSel<R::N, HasMass<R>::v != 0>::type &S, Lane<R::N, R::P> &L)
 {
     KC_SCOPE_KZ(L.kz)
     constexpr int N = R::N;
@@ -359,6 +410,7 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
         sing += 1;
         if (sing > 5u) { S.status = 5; pack(); return false; }   // Status::SingularMatrix
         S.h *= 0.5;
+        if constexpr (HasMass<R>::v) S.hhfac = 0.5;
         reject = true;
         last = false;
         if (redo_decomp) call_decomp = true;
@@ -384,7 +436,10 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
 #pragma unroll
             for (int r = 0; r < N; ++r)
 #pragma unroll
-                for (int c = 0; c < N; ++c) e1[r][c] = (r == c ? 1.0 : 0.0) * fac1 - e1[r][c];
+                for (int c = 0; c < N; ++c) {
+                    if constexpr (HasMass<R>::v) e1[r][c] = radau_mass_at<N>(a, j, r * N + c) * fac1 - e1[r][c];
+                    else e1[r][c] = (r == c ? 1.0 : 0.0) * fac1 - e1[r][c];
+                }
             S.d_nlu += 1;
             ok = bdf_lu_decomp<N>(e1, S.piv1);
             radau_mat_store<N>(a, RAD_E1, j, e1);
@@ -397,8 +452,14 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
             for (int r = 0; r < N; ++r)
 #pragma unroll
                 for (int c = 0; c < N; ++c) {
-                    e2r[r][c] = (r == c ? 1.0 : 0.0) * alphn - e2r[r][c];
-                    e2i[r][c] = (r == c ? 1.0 : 0.0) * betan;
+                    if constexpr (HasMass<R>::v) {
+                        const double m = radau_mass_at<N>(a, j, r * N + c);
+                        e2r[r][c] = m * alphn - e2r[r][c];
+                        e2i[r][c] = m * betan;
+                    } else {
+                        e2r[r][c] = (r == c ? 1.0 : 0.0) * alphn - e2r[r][c];
+                        e2i[r][c] = (r == c ? 1.0 : 0.0) * betan;
+                    }
                 }
             S.d_nlu += 1;
             ok = radau_lu_decomp_complex<N>(e2r, e2i, S.piv2);
@@ -415,7 +476,16 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
 
     double scal[N], z1[N], z2[N], z3[N], f1[N], f2[N], f3[N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) scal[i] = S.atol[i] + S.rtol[i] * fabs(S.y[i]);
+    for (int i = 0; i < N; ++i) {
+        if constexpr (HasMass<R>::v) {
+            // radau.rs:435-444: the persistent scal, divided on every pass that gets here
+            double sc = S.scal[i];
+            if (i >= S.nind1 && i < S.nind1 + S.nind2) sc = sc / S.hhfac;
+            if (i >= S.nind1 + S.nind2 && i < S.nind1 + S.nind2 + S.nind3) sc = sc / (S.hhfac * S.hhfac);   // powi(2)
+            S.scal[i] = sc;
+            scal[i] = sc;
+        } else scal[i] = S.atol[i] + S.rtol[i] * fabs(S.y[i]);
+    }
     if (first) {
 #pragma unroll
         for (int i = 0; i < N; ++i) { z1[i] = 0.0; z2[i] = 0.0; z3[i] = 0.0; f1[i] = 0.0; f2[i] = 0.0; f3[i] = 0.0; }
@@ -472,7 +542,9 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
             double sum1 = 0.0, sum2 = 0.0, sum3 = 0.0;
 #pragma unroll
             for (int jj = 0; jj < N; ++jj) {
-                const double mij = i == jj ? 1.0 : 0.0;
+                double mij;
+                if constexpr (HasMass<R>::v) mij = radau_mass_at<N>(a, j, i * N + jj);
+                else mij = i == jj ? 1.0 : 0.0;
                 sum1 -= mij * f1[jj];
                 sum2 -= mij * f2[jj];
                 sum3 -= mij * f3[jj];
@@ -514,6 +586,7 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
                     const double qnewt = fmax(1e-4, fmin(20.0, dyth));
                     const double hhfac = 0.8 * ivp_pow(qnewt, -1.0 / (4.0 + remaining), IVP_KZ_ARG);
                     S.h *= hhfac;
+                    if constexpr (HasMass<R>::v) S.hhfac = hhfac;
                     S.d_nrejct += 1;
                     last = false;
                     exit_kind = 2;
@@ -548,7 +621,10 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
         for (int i = 0; i < N; ++i) {
             double sum = 0.0;
 #pragma unroll
-            for (int jj = 0; jj < N; ++jj) sum += (i == jj ? 1.0 : 0.0) * f1[jj];
+            for (int jj = 0; jj < N; ++jj) {
+                if constexpr (HasMass<R>::v) sum += radau_mass_at<N>(a, j, i * N + jj) * f1[jj];
+                else sum += (i == jj ? 1.0 : 0.0) * f1[jj];
+            }
             f2[i] = sum;
             ce[i] = sum + S.f0[i];
         }
@@ -610,6 +686,10 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
         }
         R::ode(S.x, S.y, S.f0, L.p);
         S.d_nfev += 1;
+        if constexpr (HasMass<R>::v) {   // the only place scal is computed from y (radau.rs:711-714)
+#pragma unroll
+            for (int i = 0; i < N; ++i) S.scal[i] = S.atol[i] + S.rtol[i] * fabs(S.y[i]);
+        }
         if (FULL) {
             L.x0 = S.x0;
             // RADAU::solve builds the interpolant whenever dense_output is set, and the struct's default is true
@@ -630,11 +710,13 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
             if (theta < 0.001 && qt > 1.0 && qt < 1.2) {   // keep the step, the Jacobian and the factors
                 call_decomp = false;
                 call_jac = false;
+                if constexpr (HasMass<R>::v) S.hhfac = S.h;   // radau.rs:766
                 pack();
                 return true;
             }
             S.h = hnew;
         }
+        if constexpr (HasMass<R>::v) S.hhfac = S.h;   // radau.rs:774
         call_decomp = true;
         call_jac = theta >= 0.001;
     } else {
@@ -643,8 +725,10 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, RadauLane<R::N> &S, Lan
         last = false;
         if (first) {
             S.h *= 0.1;   // a first-step rejection is not counted
+            if constexpr (HasMass<R>::v) S.hhfac = 0.1;
         } else {
             S.d_nrejct += 1;
+            if constexpr (HasMass<R>::v) S.hhfac = hnew / S.h;
             S.h = hnew;
         }
     }
@@ -657,7 +741,7 @@ IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_
 {
     constexpr int N = R::N, P = R::P;
     const size_t B = a.B;
-    RadauLane<N> S;
+    typename RadauLaneSel<N, HasMass<R>::v != 0>::type S;
     Lane<N, P> L;
 #if defined(__HIP_DEVICE_COMPILE__) && IVP_HOIST == 2
     L.kz = ivp_opaque_zero_v();   // pinned-coefficient build: see KC() in rk_core.h
@@ -700,6 +784,16 @@ IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_
     S.d_nfev = S.d_njev = S.d_nlu = S.d_nstep = S.d_naccpt = S.d_nrejct = 0;
     S.nstep0 = a.nstep[j];
     S.naccpt0 = a.naccpt[j];
+    if constexpr (HasMass<R>::v) {
+        S.nind2 = (int)((a.ctl_nstiff >> IVP_RAD_NIND2_SHIFT) & 0xFull);
+        S.nind3 = (int)((a.ctl_nstiff >> IVP_RAD_NIND3_SHIFT) & 0xFull);
+        S.nind1 = N - S.nind2 - S.nind3;
+        S.hhfac = radau_cont(a)[(size_t)(5 * N + 2) * B + j];
+        // before the first pass that counts a step nothing has divided scal yet: it is the initial one (radau.rs:361-364)
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            S.scal[i] = S.nstep0 == 0 ? S.atol[i] + S.rtol[i] * fabs(S.y[i]) : radau_cont(a)[(size_t)(4 * N + 2 + i) * B + j];
+    }
     L.flags = S.flags & IVP_F_FIRSTOUT;
     L.x0 = S.x0;
     if (FULL) {
@@ -729,6 +823,11 @@ IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_
     radau_hold(a)[js] = S.hold;
     radau_cont(a)[(size_t)(4 * N) * B + js] = S.h_acc;
     radau_cont(a)[(size_t)(4 * N + 1) * B + js] = S.err_acc;
+    if constexpr (HasMass<R>::v) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) radau_cont(a)[(size_t)(4 * N + 2 + i) * B + js] = S.scal[i];
+        radau_cont(a)[(size_t)(5 * N + 2) * B + js] = S.hhfac;
+    }
     a.facold[js] = S.faccon;
     radau_piv(a)[js] = S.piv1;
     radau_piv(a)[B + js] = S.piv2;

@@ -1,8 +1,10 @@
 """``ivp_amd.Radau`` -- the direct per-method call ``RADAU::builder()...build().solve(..)`` (src/methods/radau.rs:19-127).
 
-Radau IIA(5), the L-stable 3-stage order-5 implicit Runge-Kutta method, on the device for pure ODEs with up to 8 states
-(identity mass matrix, strict arithmetic).  ``solve_ivp(..., Options(method="RADAU"))`` still answers
-``IVP_ERR_UNSUPPORTED_METHOD``; this class is the way in, and it carries the struct fields ``solve_ivp`` cannot reach.
+Radau IIA(5), the L-stable 3-stage order-5 implicit Runge-Kutta method, on the device for systems with up to 8 states
+(strict arithmetic): pure ODEs, and ``M y' = f(t, y)`` with a constant, possibly singular mass matrix -- a
+``DeviceIVP(..., mass=True)`` -- and index-1/2/3 algebraic variables (``nind1`` / ``nind2`` / ``nind3``).
+``solve_ivp(..., Options(method="RADAU"))`` still answers ``IVP_ERR_UNSUPPORTED_METHOD``; this class is the way in, and it
+carries the struct fields ``solve_ivp`` cannot reach.
 """
 from typing import Optional, Sequence
 
@@ -12,10 +14,14 @@ from . import _lib, api
 class Radau:
     """The fields of ``struct RADAU`` that ``Options`` does not carry; ``rtol`` / ``atol`` / ``max_steps`` / ``t_eval`` /
     ``first_step`` / ``max_step`` / ``min_step`` / ``dense_output`` / ``max_log`` come from the ``Options`` given to
-    ``solve`` / ``solve_batch`` (its ``method`` is ignored; ``max_steps=None`` means unlimited, as in ``solve_ivp``)."""
+    ``solve`` / ``solve_batch`` (its ``method`` is ignored; ``max_steps=None`` means unlimited, as in ``solve_ivp``).
+    ``nind1`` / ``nind2`` / ``nind3``: the counts of index-1, index-2 and index-3 variables, in that order in the state
+    (radau.rs:210-246: all ``None`` = a pure ODE partition; ``nind1`` omitted = inferred; else they must sum to n, or
+    ``ConfigError`` with code -7).  Index-2 / index-3 variables need a problem with a mass matrix."""
 
     def __init__(self, newton_maxiter: int = 7, newton_tol: Optional[float] = None, predictive: bool = True,
-                 uround: float = 2.3e-16, safety_factor: float = 0.9, scale_min: float = 0.2, scale_max: float = 8.0):
+                 uround: float = 2.3e-16, safety_factor: float = 0.9, scale_min: float = 0.2, scale_max: float = 8.0,
+                 nind1: Optional[int] = None, nind2: Optional[int] = None, nind3: Optional[int] = None):
         self.newton_maxiter = int(newton_maxiter)
         self.newton_tol = None if newton_tol is None else float(newton_tol)
         self.predictive = bool(predictive)
@@ -23,6 +29,9 @@ class Radau:
         self.safety_factor = float(safety_factor)
         self.scale_min = float(scale_min)
         self.scale_max = float(scale_max)
+        self.nind1 = None if nind1 is None else int(nind1)
+        self.nind2 = None if nind2 is None else int(nind2)
+        self.nind3 = None if nind3 is None else int(nind3)
 
     def _c(self) -> _lib.RadauSettingsT:
         s = _lib.RadauSettingsT()
@@ -33,12 +42,23 @@ class Radau:
         s.predictive = 1 if self.predictive else 0
         return s
 
+    def _dae(self, f: api.IVP = None) -> Optional[_lib.RadauDaeT]:
+        """The partition for ``ivp_radau_solve_dae*``, or None: the DAE entry point is taken only for a problem with a mass
+        matrix or a given partition, everything else takes the path it took."""
+        if not (getattr(f, "has_mass", False) or any(v is not None for v in (self.nind1, self.nind2, self.nind3))):
+            return None
+        d = _lib.RadauDaeT()
+        d.has_nind1, d.nind1 = (0, 0) if self.nind1 is None else (1, self.nind1)
+        d.has_nind2, d.nind2 = (0, 0) if self.nind2 is None else (1, self.nind2)
+        d.has_nind3, d.nind3 = (0, 0) if self.nind3 is None else (1, self.nind3)
+        return d
+
     def solve(self, f: api.IVP, t0: float, t1: float, y0: Sequence[float], options: api.Options = None,
               ctx: api.Context = None) -> api.Solution:
         """One trajectory; the ``Solution`` that ``DefaultSolOut`` records (every accepted step, or the ``t_eval`` samples)."""
-        return api.solve_ivp(f, t0, t1, y0, options, ctx, _radau=self._c())
+        return api.solve_ivp(f, t0, t1, y0, options, ctx, _radau=self._c(), _radau_dae=self._dae(f))
 
     def solve_batch(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None, ctx: api.Context = None,
                     out: api.BatchSolution = None) -> api.BatchSolution:
         """B independent ``solve`` calls; host (numpy) or device (torch) arrays, like ``solve_ivp_batch``."""
-        return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, _radau=self._c())
+        return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, _radau=self._c(), _radau_dae=self._dae(f))

@@ -29,6 +29,7 @@ pub const IVP_ERR_NEGATIVE_TOLERANCE: c_int = -3;
 pub const IVP_ERR_TOLERANCE_SIZE_MISMATCH: c_int = -4;
 pub const IVP_ERR_INVALID_STEP_SIZE: c_int = -5;
 pub const IVP_ERR_INVALID_SCALE_FACTORS: c_int = -6;
+pub const IVP_ERR_INVALID_DAE_PARTITION: c_int = -7;
 pub const IVP_ERR_BAD_ARGUMENT: c_int = -100;
 pub const IVP_ERR_UNSUPPORTED_METHOD: c_int = -101;
 pub const IVP_ERR_NO_DEVICE: c_int = -102;
@@ -39,6 +40,7 @@ pub const IVP_ERR_LOG_CAPACITY: c_int = -105;
 pub const IVP_RHS_JIT: i32 = 1000;
 pub const IVP_RHS_HAS_JAC: u32 = 1;
 pub const IVP_RHS_BANDED: u32 = 2;
+pub const IVP_RHS_HAS_MASS: u32 = 4;
 
 #[repr(C)]
 pub struct ivp_problem_t {
@@ -132,6 +134,18 @@ pub struct ivp_radau_settings_t {
     pub has_newton_tol: i32,
     pub predictive: i32,
     pub reserved: i32,
+}
+
+/// `nind1` / `nind2` / `nind3` of the `RADAU` struct (`Option<usize>` each: `has_x == 0` is `None`), for `ivp_radau_solve_dae*`.
+#[repr(C)]
+pub struct ivp_radau_dae_t {
+    pub has_nind1: i32,
+    pub nind1: i32,
+    pub has_nind2: i32,
+    pub nind2: i32,
+    pub has_nind3: i32,
+    pub nind3: i32,
+    pub reserved: [i32; 2],
 }
 
 #[repr(C)]
@@ -261,6 +275,16 @@ extern "C" {
     pub fn ivp_radau_solve_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
                                   t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
                                   settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
+    // ... for M y' = f with a constant mass matrix (IVP_RHS_HAS_MASS) and the DAE index sets
+    pub fn ivp_radau_dae_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,
+                               dae: *const ivp_radau_dae_t, message: *mut c_char, message_len: usize) -> c_int;
+    pub fn ivp_radau_solve_dae(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                               t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                               settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t) -> c_int;
+    pub fn ivp_radau_solve_dae_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                      t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                      settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                      hip_stream: *mut c_void) -> c_int;
     // Solution.t / Solution.y in ONE call and ONE integration (page pool + gather kernel)
     pub fn ivp_batch_solve_logged_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64,
                                          params: *const f64, t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize,

@@ -19,4 +19,6 @@ run group_strict rk_group.hip -DIVP_FAST=0 &
 run group_fma   rk_group.hip -DIVP_FAST=1 &
 wait
 run radau_strict rk_radau.hip -DIVP_FAST=0 &
+# the mass-matrix instantiations of the Radau kernels (hiprtc modules only): tools/radau_dae_resources.hip, n = 1, 2, 3, 5, 8
+run radau_dae "$TOOLS/radau_dae_resources.hip" -DIVP_FAST=0 -I. &
 wait
