@@ -34,7 +34,7 @@ extern "C" {
 
 /* Method: same order as `enum Method`, src/solve/options.rs:14-27. The explicit RK methods (RK23, DOPRI5,
  * DOP853, the fixed-step RK4) and the variable-order implicit BDF are on the accelerated path of solve_ivp().  RADAU
- * runs on the device through its direct per-method call, ivp_radau_solve*() below (n <= 8); as ivp_options_t.method
+ * runs on the device through its direct per-method call, ivp_radau_solve*() below (n <= 64); as ivp_options_t.method
  * it still returns IVP_ERR_UNSUPPORTED_METHOD from the solve_ivp() entry points. */
 typedef enum {
     IVP_RK23 = 0,
@@ -338,8 +338,10 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
 
 /*
  * Radau IIA(5), the direct per-method call: B independent RADAU::builder()...build().solve(f, x0, y0, xend, rtol, atol,
- * Some(&mut DefaultSolOut)) calls (src/methods/radau.rs:19-127) for pure ODEs with the identity mass matrix, n <= 8,
- * strict arithmetic.  ivp_radau_settings_t carries the struct fields solve_ivp() cannot reach; the fields it can come
+ * Some(&mut DefaultSolOut)) calls (src/methods/radau.rs:19-127) for pure ODEs with the identity mass matrix, n <= 64,
+ * strict arithmetic: one lane per trajectory for n <= 8; for 8 < n <= 64 (the built-in IVP_RHS_DENSE_64, and hiprtc problems
+ * in component form, ode_comp with an optional jac_col) one group of 16 / 32 / 64 lanes per trajectory, one matrix row per
+ * lane, the three factors of the attempt resident in LDS -- 3 n^2 doubles, which is what sets the bound.  ivp_radau_settings_t carries the struct fields solve_ivp() cannot reach; the fields it can come
  * from ivp_options_t: rtol / atol (scalar or vector), max_steps (0 = unlimited, the solve_ivp convention), t_eval with
  * or without t_eval_offsets, first_step, max_step, min_step, dense_output, max_log, chunk_attempts, profile.
  * opt->method is ignored.  Arguments otherwise as for ivp_batch_solve_device / ivp_batch_solve; settings == NULL means
@@ -347,9 +349,10 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  * [coef][component]; ivp_dense_eval_device(method = IVP_RADAU) evaluates them.
  * Errors, reported before the device is touched: the ConfigErrors of radau.rs:132-262 (MUST_BE_POSITIVE: newton_maxiter;
  * OUT_OF_RANGE: uround, safety_factor, newton_maxiter > 15; INVALID_SCALE_FACTORS; INVALID_STEP_SIZE: first_step == 0;
- * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 8, problems
- * with event functions, fp_mode = FMA and variant = 3.  Banded storage and the CSR one-pass / dense / events /
- * multi-device forms are not on this path yet.
+ * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 64, problems
+ * with event functions, fp_mode = FMA, variant = 3 and, for n > 8, a problem compiled with IVP_RHS_BANDED or with a
+ * jac_sparsity pattern (ivp_rhs_compile_sparse).  The CSR one-pass / dense / events / multi-device forms are not on this
+ * path yet.
  *
  * M y' = f(t, y) with a constant, possibly singular mass matrix and index-1/2/3 algebraic variables: ivp_radau_solve_dae*()
  * and ivp_radau_dae_check(), the three calls above plus `dae`.  The mass matrix comes from the problem -- a hiprtc snippet
@@ -361,7 +364,9 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  * negative count (not expressible in the reference) gets the same error.  Variables are ordered index-1 first, then
  * index-2, then index-3; the error scale of an index-2 (index-3) variable is divided by the step ratio hhfac (hhfac^2)
  * on every attempt (radau.rs:435-444).  nind2 + nind3 > 0 for a problem WITHOUT the mass hook is IVP_ERR_BAD_ARGUMENT
- * ("not yet").  The refusals above (n > 8, events, FMA, variant = 3) apply unchanged.
+ * ("not yet").  The refusals above (n > 64, events, FMA, variant = 3, banded storage and patterns beyond n = 8) apply
+ * unchanged; a mass matrix and index-2 / index-3 variables stay n <= 8 (IVP_RHS_HAS_MASS), and a pure index-1 partition
+ * of a larger problem takes the path of ivp_radau_solve*().
  * Deliberate deviation: a problem compiled with IVP_RHS_HAS_MASS is refused (IVP_ERR_BAD_ARGUMENT) by every other entry
  * point, ivp_radau_solve*() included -- the reference's explicit methods and BDF ignore IVP::mass silently, which solves a
  * different equation without saying so.

@@ -195,6 +195,7 @@ hipError_t pend_launch(ivp_ctx *ctx, int what, const IvpKArgs &ka, uint32_t lane
     hipStream_t s = P.stream;
     const bool fast = P.fp_mode == IVP_FP_FAST;
     if (P.jit) return ivp_jit_launch(P.prob.jit, (use_coop && what == IVP_LAUNCH_CHUNK) ? IVP_LAUNCH_COOP : what, P.method, P.fp_mode, P.full, ka, lanes, s);
+    if (P.group && P.method == IVP_RADAU) return ivp_launch_radau_group_strict(what, P.prob.rhs_id, P.full, ka, lanes, s);
     if (P.group) return (fast ? ivp_launch_group_fast : ivp_launch_group_strict)(what, P.method, P.prob.rhs_id, P.full, ka, lanes, s);
     if (P.method == IVP_RADAU) return ivp_launch_radau_strict(what, P.prob.rhs_id, P.full, ka, lanes, s);
     if (P.method == IVP_BDF) {
@@ -649,8 +650,14 @@ int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_
     const int rc = validate(ctx, prob, B, opt, n_out, p_out, rad->dae_call ? IVP_VALIDATE_RADAU_DAE : IVP_VALIDATE_RADAU);
     if (rc != IVP_OK) return rc;
     const int n = *n_out;
-    if (n > IVP_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_MAX_N);
-    const int n_events = prob->rhs_id == IVP_RHS_JIT ? ivp_jit_n_events(prob->jit) : kRhsEvents[prob->rhs_id];
+    if (n > IVP_RADAU_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_RADAU_MAX_N);
+    if (n > IVP_MAX_N && prob->rhs_id == IVP_RHS_JIT) {   // radau_group.h factorises full matrices from a full Jacobian
+        if (ivp_jit_band(prob->jit, nullptr, nullptr, nullptr))
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for a problem compiled with IVP_RHS_BANDED (n = %d): not yet", n);
+        if (ivp_jit_has_sparsity(prob->jit))
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for a problem with a jac_sparsity pattern (n = %d): not yet", n);
+    }
+    const int n_events = prob->rhs_id == IVP_RHS_JIT ? ivp_jit_n_events(prob->jit) : n > IVP_MAX_N ? 0 : kRhsEvents[prob->rhs_id];
     if (n_events > 0) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for problems with event functions: not yet on the accelerated path");
     if (opt->fp_mode != IVP_FP_STRICT) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with fp_mode = FMA: not yet (strict arithmetic only)");
     if (opt->variant == 3) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with variant = 3 (lane-cooperative kernels): not yet");
@@ -804,11 +811,12 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         BIND(njev, out->njev, sc_njev, sizeof(uint64_t) * B);
         BIND(nlu, out->nlu, sc_nlu, sizeof(uint64_t) * B);
         // Radau's state lives behind the BDF members of the argument block (ivp_kargs.h), in buffers of its own
+        // (n > 8, radau_group.h: the matrices are one contiguous column-major block [J, E1, E2r, E2i] per trajectory: same size)
         // ... a problem with a mass matrix keeps M behind the four matrices, and scal[n] and hhfac behind cont (radau_core.h)
         const bool has_mass = prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit);
         HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (has_mass ? 5 : 4) * n * n * B));
         HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (has_mass ? 5 * n + 3 : 4 * n + 2) * B));
-        HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B));
+        HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B * (group ? (size_t)n : 1)));   // n > 8 (radau_group.h): [B][2][n] pivot rows
         a.bdf_jac = (double *)ctx->rad_mat.p;
         a.bdf_d = (double *)ctx->rad_cont.p;
         a.bdf_piv = (uint32_t *)ctx->rad_piv.p;

@@ -163,9 +163,11 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
     s += "#define IVP_USER_NE " + std::to_string(r.ne) + "\n";
     s += std::string("#define IVP_USER_JAC ") + (r.has_jac ? "1" : "0") + "\n";
     const bool group = r.n > IVP_MAX_N;   // wave-per-trajectory kernels (rk_group.h): user code defines ode_comp()
-    const bool radau = method == IVP_RADAU;   // radau_core.h: thread per trajectory, n <= 8, built like rk_radau.hip
-    if (group || coop_only || radau) s += "#define IVP_HOIST 2\n";   // a wave that owns its SIMD: coefficients pinned in registers (rk_core.h KC)
-    if (radau) s += "#define IVP_MIN_WAVES 1\n";
+    const bool radau = method == IVP_RADAU;   // radau_core.h: thread per trajectory, n <= 8, built like rk_radau.hip; radau_group.h beyond
+    // a wave that owns its SIMD: coefficients pinned in registers (rk_core.h KC) -- but not the group Radau kernels, which
+    // would spill to scratch (rk_radau_group.hip)
+    if ((group || coop_only || radau) && !(group && radau)) s += "#define IVP_HOIST 2\n";
+    if (radau && !group) s += "#define IVP_MIN_WAVES 1\n";
     const bool mass = radau && r.has_mass;   // only the Radau modules of a problem with the hook: every other module's source stays what it was
     if (mass) s += "#define IVP_USER_MASS 1\n";
     s += join(k_src_ivp_kargs_h);
@@ -179,6 +181,22 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
         s += join(k_src_rk_global_h);   // compact_append
         s += join(k_src_rk_group_h);
         s += join(k_src_bdf_group_h);
+        if (radau) {   // radau_group.h: 8 < n <= 64 (the host refuses everything else), G >= n lanes per trajectory
+            s += join(k_src_radau_core_h);
+            s += join(k_src_radau_group_h);
+            std::snprintf(buf, sizeof buf,
+                          "namespace ivp_jit { struct RhsUser { enum { N = %d, P = %d, NE = IVP_USER_NE };\n"
+                          "  static __device__ __forceinline__ double ode_comp(int i, double x, const double* y, const double* p) { return ::ode_comp(i, x, y, p); }\n"
+                          "#if IVP_USER_JAC\n"
+                          "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
+                          "#endif\n"
+                          "}; }\n"
+                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::radau_group_init_kernel_body<ivp_jit::RhsUser, %s, %d>(a); }\n"
+                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::radau_group_chunk_kernel_body<ivp_jit::RhsUser, %s, %d>(a); }\n",
+                          r.n, r.np, flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
+            s += buf;
+            return s;
+        }
         // the pattern is read by BDF only (the explicit methods never call jac): other modules compile to what they were
         const bool sparse = method == IVP_BDF && !r.sparsity_source.empty();
         std::string sp;
@@ -434,6 +452,8 @@ bool ivp_jit_band(void *handle, int *ml, int *mu, bool *lds_fits)
     if (lds_fits) *lds_fits = band_lds_fits(r->n, r->band_ml, r->band_mu, r->ne);
     return true;
 }
+
+bool ivp_jit_has_sparsity(void *handle) { return handle && ((JitRhs *)handle)->n_groups > 0; }
 
 void ivp_jit_dims(void *handle, int *n, int *np)
 {

@@ -13,6 +13,7 @@ void ivp_jit_free(void *handle);
 // banded storage (IVP_RHS_BANDED): true and the bandwidths for a banded problem; lds_fits: the factors of a trajectory fit
 // the LDS budget of the banded kernels (bdf_band.h)
 bool ivp_jit_band(void *handle, int *ml, int *mu, bool *lds_fits);
+bool ivp_jit_has_sparsity(void *handle);   // compiled with a jac_sparsity pattern (ivp_rhs_compile_sparse)
 void ivp_jit_dims(void *handle, int *n, int *n_params);
 const char *ivp_jit_last_log(void *handle);   // hiprtc build log / load error of the most recent failure
 hipError_t ivp_jit_launch(void *handle, int what, int method, int fp_mode, int full, const IvpKArgs &a,

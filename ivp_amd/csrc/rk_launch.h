@@ -41,3 +41,8 @@ hipError_t ivp_launch_bdf_fast_occ2(int what, int rhs_id, int full, const IvpKAr
 // thread-per-trajectory Radau IIA(5) kernels (rk_radau.hip: pinned-coefficient build, strict arithmetic, n <= 8,
 // built-in right-hand sides 0-10 and 15)
 hipError_t ivp_launch_radau_strict(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t lanes, hipStream_t s);
+// group-per-trajectory Radau IIA(5) kernels (rk_radau_group.hip: radau_group.h, strict arithmetic, 8 < n <= 64: built-in
+// right-hand side 102); grid = `trajectories` one-wave blocks
+hipError_t ivp_launch_radau_group_strict(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t trajectories, hipStream_t s);
+// largest n of the Radau path: the three factors of a trajectory (3 n^2 doubles) stay resident in LDS (radau_group.h)
+#define IVP_RADAU_MAX_N 64

@@ -264,7 +264,7 @@ extern "C" {
                                    out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
     pub fn ivp_batch_poll(ctx: *mut ivp_ctx_t, done: *mut c_int) -> c_int;
     pub fn ivp_batch_wait(ctx: *mut ivp_ctx_t) -> c_int;
-    // Radau IIA(5), the direct per-method call (RADAU::builder()...build().solve(..)), n <= 8
+    // Radau IIA(5), the direct per-method call (RADAU::builder()...build().solve(..)), n <= 64 (a mass matrix and index-2/3 variables: n <= 8)
     pub fn ivp_radau_settings_default(settings: *mut ivp_radau_settings_t);
     pub fn ivp_options_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, message: *mut c_char, message_len: usize) -> c_int;
     pub fn ivp_radau_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,

@@ -22,3 +22,7 @@ run radau_strict rk_radau.hip -DIVP_FAST=0 &
 # the mass-matrix instantiations of the Radau kernels (hiprtc modules only): tools/radau_dae_resources.hip, n = 1, 2, 3, 5, 8
 run radau_dae "$TOOLS/radau_dae_resources.hip" -DIVP_FAST=0 -I. &
 wait
+run radau_group_strict rk_radau_group.hip -DIVP_FAST=0 &
+# the group-per-trajectory Radau kernels (radau_group.h) at n = 9, 16, 32, 33, 64: tools/radau_group_resources.hip
+run radau_group "$TOOLS/radau_group_resources.hip" -DIVP_FAST=0 -I. &
+wait
