@@ -191,8 +191,8 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                           "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
                           "#endif\n"
                           "}; }\n"
-                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::radau_group_init_kernel_body<ivp_jit::RhsUser, %s, %d>(a); }\n"
-                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::radau_group_chunk_kernel_body<ivp_jit::RhsUser, %s, %d>(a); }\n",
+                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n"
+                          "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n",
                           r.n, r.np, flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
             s += buf;
             return s;

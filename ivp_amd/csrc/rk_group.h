@@ -160,7 +160,8 @@ struct NormOps<GroupRhs<R, G>, void> {
     }
 };
 
-// BDF for large n (bdf_group.h, included after this header)
+// BDF for large n (bdf_group.h, included after this header).  Radau IIA(5) needs no bodies of its own: radau_core.h's run on
+// GroupRhs<R, G> like the explicit methods' do (radau_group.h holds their policy for 8 < n <= 64).
 template <class R, int FULL, int G>
 __device__ __forceinline__ int32_t bdf_group_init_body(const IvpKArgs &a, uint32_t j);
 template <class R, int FULL, int G, bool LDSLU>
@@ -173,6 +174,7 @@ __device__ __forceinline__ void group_init_body(const IvpKArgs &a)
     const uint32_t j = blockIdx.x * (IVP_WAVE / G) + threadIdx.x / G;
     if (j >= a.B) return;
     if constexpr (M == M_BDF) (void)bdf_group_init_body<R, FULL, G>(a, j);
+    else if constexpr (M == M_RADAU) (void)radau_init_body<GroupRhs<R, G>, FULL>(a, j);   // radau_core.h over radau_group.h's policy
     else (void)init_body<M, GroupRhs<R, G>, FULL>(a, j);
 }
 
@@ -197,6 +199,7 @@ __device__ __forceinline__ void group_chunk_body(const IvpKArgs &a)
     constexpr bool kCtl = M == M_RK23 || M == M_DOPRI5 || M == M_DOP853;
     if (active) {
         if constexpr (M == M_BDF) it = bdf_group_chunk_body<R, FULL, G, LDSLU>(a, j, st);
+        else if constexpr (M == M_RADAU) it = radau_chunk_body<GroupRhs<R, G>, FULL>(a, j, st);
         else it = chunk_body<M, GroupRhs<R, G>, FULL, kCtl>(a, j, st);
     }
     const bool lead = (threadIdx.x & (G - 1)) == 0;

@@ -1,4 +1,5 @@
-// rk_radau_group.hip -- group-per-trajectory Radau IIA(5) kernels (radau_group.h, 8 < n <= 64) and their launch table.
+// rk_radau_group.hip -- group-per-trajectory Radau IIA(5) kernels (group_init_kernel / group_chunk_kernel of rk_group.h with
+// M_RADAU: radau_core.h's bodies over radau_group.h's policy, 8 < n <= 64) and their launch table.
 //
 // Built like the BDF group kernels of rk_group.hip -- one wavefront per workgroup, strict arithmetic (the only build: the
 // Radau attempt has no fused site) -- except for the coefficients: IVP_HOIST = 0, the lean form of KC() in rk_core.h.  With
@@ -30,8 +31,8 @@ hipError_t launch_one(int what, const IvpKArgs &a, uint32_t trajectories, hipStr
     const dim3 grid(trajectories), block(IVP_WAVE);   // built-in problems: one wavefront per trajectory
     if (grid.x == 0) return hipSuccess;
     (void)hipGetLastError();   // drop a stale error of some earlier runtime call: the value returned below is this launch's
-    if (what == IVP_LAUNCH_INIT) hipLaunchKernelGGL((IVP_NS::radau_group_init_kernel<R, FULL>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((IVP_NS::radau_group_chunk_kernel<R, FULL>), grid, block, 0, s, a);
+    if (what == IVP_LAUNCH_INIT) hipLaunchKernelGGL((IVP_NS::group_init_kernel<IVP_NS::M_RADAU, R, FULL>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((IVP_NS::group_chunk_kernel<IVP_NS::M_RADAU, R, FULL>), grid, block, 0, s, a);
     return hipGetLastError();
 }
 

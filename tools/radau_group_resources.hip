@@ -41,9 +41,9 @@ struct ResDense<NN_, true> : ResDense<NN_, false> {
 };
 
 template <int NN_, bool JAC, int FULL, int G>
-__global__ __launch_bounds__(IVP_WAVE) void res_init(const IvpKArgs a) { radau_group_init_kernel_body<ResDense<NN_, JAC>, FULL, G>(a); }
+__global__ __launch_bounds__(IVP_WAVE) void res_init(const IvpKArgs a) { group_init_body<M_RADAU, ResDense<NN_, JAC>, FULL, G>(a); }
 template <int NN_, bool JAC, int FULL, int G>
-__global__ __launch_bounds__(IVP_WAVE) void res_chunk(const IvpKArgs a) { radau_group_chunk_kernel_body<ResDense<NN_, JAC>, FULL, G>(a); }
+__global__ __launch_bounds__(IVP_WAVE) void res_chunk(const IvpKArgs a) { group_chunk_body<M_RADAU, ResDense<NN_, JAC>, FULL, G>(a); }
 
 #define RES(n, g)                                                     \
     template __global__ void res_init<n, false, 1, g>(const IvpKArgs);  \
