@@ -893,5 +893,12 @@ IVP_HD uint32_t any_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_ou
     else if constexpr (M == M_RADAU) return radau_chunk_body<R, FULL>(a, j, status_out);
     else return chunk_body<M, R, FULL, CTL>(a, j, status_out);
 }
+// ... with the attempt count given by the caller (a piece of a balanced round, ivp_balance.h): explicit RK methods only
+template <int M, class R, int FULL, bool CTL = false>
+IVP_HD uint32_t any_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out, uint32_t attempts)
+{
+    static_assert(M != M_BDF && M != M_RADAU, "explicit RK methods only");
+    return chunk_body<M, R, FULL, CTL, true>(a, j, status_out, attempts);
+}
 
 }  // namespace IVP_NS

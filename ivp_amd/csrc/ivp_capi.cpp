@@ -21,6 +21,7 @@
 
 #include "ivp_jit.h"
 #include "ivp_kargs.h"
+#include "ivp_balance.h"
 #include "rk_launch.h"
 #include "ivp_ctx.h"
 
@@ -156,6 +157,9 @@ struct Tune {
     int defer_eval = 1;              // DOP853 t_eval sampling in a second, sample-parallel kernel (flavour 3): 0 = sample in the stepping kernel
     int defer_events = 1;            // event roots (no terminal event) in a second kernel, one lane per step with a crossing: 0 = Brent in the stepping kernel
     int bdf_lpw = 0;                 // trajectories per wave of the BDF chunk launches: 0 = auto (spread the active set over the SIMDs)
+    int balance = 1;                 // balanced bulk rounds (ivp_balance.h) where windows would run: 1 = automatic, 0 = windows
+    uint32_t balance_slots = 0;      // != 0: plan windows and balanced rounds as if the device had this many wave slots (tests: a few
+                                     // hundred trajectories then take every path of the plan)
     Tune()
     {
         if (const char *e = getenv("IVP_TUNE_COOP_CAP_LANES")) coop_cap_lanes = (size_t)strtoull(e, nullptr, 10);
@@ -166,6 +170,8 @@ struct Tune {
         if (const char *e = getenv("IVP_TUNE_DEFER_EVAL")) defer_eval = (int)strtol(e, nullptr, 10);
         if (const char *e = getenv("IVP_TUNE_DEFER_EVENTS")) defer_events = (int)strtol(e, nullptr, 10);
         if (const char *e = getenv("IVP_TUNE_BDF_LPW")) bdf_lpw = (int)std::min(64l, std::max(0l, strtol(e, nullptr, 10)));
+        if (const char *e = getenv("IVP_TUNE_BALANCE")) balance = (int)strtol(e, nullptr, 10);
+        if (const char *e = getenv("IVP_TUNE_BALANCE_SLOTS")) balance_slots = (uint32_t)std::min(1l << 20, std::max(0l, strtol(e, nullptr, 10)));
         if (const char *e = getenv("IVP_TUNE_LAUNCHES_PER_POLL")) { launches_per_poll = (int)std::min(16l, std::max(1l, strtol(e, nullptr, 10))); launches_per_poll_set = 1; }
     }
 };
@@ -289,6 +295,8 @@ int enqueue_round(ivp_ctx *ctx)
     // pass their entries on; those land first in the output list, so every trajectory is at most one launch behind.
     // Results never depend on how attempts are cut into launches.
     uint32_t window = 0;
+    const uint32_t slots = tune().balance_slots ? tune().balance_slots : kOneWavePerSimd / (uint32_t)IVP_WAVE;   // wave slots
+    IvpBalancePlan plan = {0u, 0u, 0u};
     // (not for problems with event functions: the root-finding of a crossing is a long divergent stretch that a second wave
     // on the SIMD hides; measured on C2 with the x-axis crossing event 4.5 ms with full launches, 5.0 with windows.  With
     // deferred refinement there is no such stretch, but the full DefaultSolOut kernel gains nothing from windows either:
@@ -298,12 +306,21 @@ int enqueue_round(ivp_ctx *ctx)
     const bool alone = inflight_on(ctx->device).load(std::memory_order_relaxed) <= 1;
     if (tune().window && alone && P.adaptive && !P.group && !use_coop && !tail && lpw == 0 && P.method != IVP_BDF && P.method != IVP_RADAU && !P.has_events &&
         (P.n >= 4 || tune().window == 2)) {
-        const uint32_t full = lanes / kOneWavePerSimd;
-        if (full >= 1 && full < 4 && (uint64_t)lanes * 5u < (uint64_t)(full + 1u) * kOneWavePerSimd * 4u) window = full * kOneWavePerSimd;
+        // one to four slot-fulls whose last wave-round would be less than ~80 % full (IVP_TUNE_BALANCE_SLOTS: a pretended device)
+        window = ivp_balance_window(lanes, slots);
+        // Balanced rounds (ivp_balance.h).  Windows still pay for whole launches: C2's 1563 waves need 1563 x 192 = 300 096
+        // wave-attempts to reach the hand-over and get 5 launches x 1024 slots x 64 attempts = 327 680, the fifth launch
+        // running ~715 waves on 1024 SIMDs for as long as a full one; and which trajectories sit in the launches that run
+        // ahead depends on the order waves reach compact_append's atomic, so the tail starts from 192, 256 or 320 attempts.
+        // The plan cuts the round's nb x R attempts into L launches of at most q attempts per workgroup instead, every
+        // workgroup but the trailing ones stepping exactly q: C2 runs 5 launches of 59 attempts, 5087 of 5120 slots used,
+        // and every trajectory reaches the end of the round with exactly R attempts.
+        if (window && tune().balance && !P.jit && ivp_has_balanced(P.method, P.prob.rhs_id, P.full, P.a.has_ctl))
+            plan = ivp_balance_plan(lanes, (uint32_t)tune().launches_per_poll * this_chunk, slots, this_chunk);
         // a round still covers `launches_per_poll` chunks of the WHOLE list (a host poll idles the GPU for ~50 us)
         if (window) launches_per_sync = (int)(((uint64_t)launches_per_sync * lanes + window - 1u) / window);
         // what runs at once is the window, not the list: at most two waves per SIMD take the resident build
-        if (window && !P.has_settings && P.variant == 0 && (size_t)window <= 2 * (size_t)kOneWavePerSimd) use_hoist = true;
+        if (window && !P.has_settings && P.variant == 0 && ((size_t)window <= 2 * (size_t)slots * IVP_WAVE || plan.L)) use_hoist = true;
     }
     // Paired launches.  For a problem whose stragglers go to the lane-cooperative kernels, every bulk launch of a round
     // is followed by a cooperative launch on the SAME input / output lists: the bulk one works while more than T
@@ -321,6 +338,36 @@ int enqueue_round(ivp_ctx *ctx)
         if (!profile || !paired || P.step_ev.size() >= kMaxRanSlots) return nullptr;
         return (uint32_t *)ctx->ran.p + P.step_ev.size();
     };
+    if (plan.L) {
+        // A balanced round: L launches on ONE input list and ONE output list (one value of c: the lists and counters rotate
+        // once per round), then the usual (bulk, cooperative) pair on the round's output list -- one declining partner per
+        // round instead of one per launch.  The host knows the count these launches start from (it is the one just polled,
+        // or B), so they carry neither spec_min nor a ran flag: they always work.
+        const uint64_t c = P.c;
+        const uint32_t R = (uint32_t)tune().launches_per_poll * this_chunk;
+        for (uint32_t l = 0; l < plan.L; ++l) {
+            IvpKArgs ka = P.a;
+            ka.chunk = plan.q;
+            ka.balance = ivp_balance_pack(R, plan.L, l);
+            ka.lpw = 0u;
+            ka.window = 0u;
+            ka.spec_min = 0u;
+            ka.ran_out = nullptr;
+            ka.lds_lu = 0u;
+            ka.perm_in = c == 0 ? nullptr : (const uint32_t *)ctx->perm[(c - 1) & 1].p;
+            ka.count_in = c == 0 ? nullptr : counts + ((c - 1) & 3);
+            ka.perm_out = (uint32_t *)ctx->perm[c & 1].p;
+            ka.count_out = counts + (c & 3);
+            ka.count_next = counts + ((c + 1) & 3);   // nobody reads it before the round's last launch has reset it again
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (profile) { e0 = pend_event(ctx); HIP_TRY(ctx, hipEventRecord(e0, s)); }
+            LAUNCH_TRY(ctx, pend_launch(ctx, IVP_LAUNCH_BALANCED, ka, plan.W * (uint32_t)IVP_WAVE, use_hoist, false));
+            if (profile) { e1 = pend_event(ctx); HIP_TRY(ctx, hipEventRecord(e1, s)); P.step_ev.emplace_back(e0, e1); P.step_is_coop.push_back(4); P.step_lanes.push_back(lanes); }
+            if (!profile) ctx->stats.launches += 1;
+        }
+        ++P.c;
+        launches_per_sync = (paired && tune().launches_per_poll_set == 0) ? 1 : 0;
+    }
     for (int r = 0; r < launches_per_sync; ++r, ++P.c) {
         const uint64_t c = P.c;
         IvpKArgs ka = P.a;
@@ -449,11 +496,11 @@ int finish_round(ivp_ctx *ctx, int *done)
         // count as stepping time of the kernel kind that ran, and it is not counted as a launch)
         std::vector<uint32_t> ran(std::min(P.step_ev.size(), (size_t)kMaxRanSlots), 1u);
         if (!ran.empty()) HIP_TRY(ctx, hipMemcpy(ran.data(), ctx->ran.p, ran.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t q = 0; q < P.step_ev.size(); ++q) {   // step_is_coop: bit 0 = cooperative kernel, bit 1 = half of a pair (has a ran flag)
+        for (size_t q = 0; q < P.step_ev.size(); ++q) {   // step_is_coop: bit 0 = cooperative kernel, bit 1 = half of a pair (has a ran flag), bit 2 = launch of a balanced round
             HIP_TRY(ctx, hipEventElapsedTime(&ms, P.step_ev[q].first, P.step_ev[q].second));
             const bool coop = (P.step_is_coop[q] & 1) != 0, flagged = (P.step_is_coop[q] & 2) != 0;
             const bool did = !flagged || q >= ran.size() || ran[q] != 0;
-            if (trace_launches()) fprintf(stderr, "ivp launch %3zu  %-4s %-8s lanes<=%-8u %8.4f ms\n", q, coop ? "coop" : "bulk", did ? "ran" : "declined", P.step_lanes[q], ms);
+            if (trace_launches()) fprintf(stderr, "ivp launch %3zu  %-4s %-8s lanes<=%-8u %8.4f ms\n", q, coop ? "coop" : ((P.step_is_coop[q] & 4) ? "bal" : "bulk"), did ? "ran" : "declined", P.step_lanes[q], ms);
             ctx->stats.step_kernel_ms += ms;
             if (coop) ctx->stats.coop_kernel_ms += ms;
             if (did) {

@@ -176,6 +176,11 @@ struct IvpKArgs {
     double *evd_rec;          // [evd_cap][F][B] noted steps, F = 4 + 3 NE + n + NCoef n (EvdRec); NULL: roots are found in the stepping kernel
     uint32_t *evd_cnt;        // [B] noted steps of a trajectory
     uint32_t evd_cap;         // noted steps per trajectory the buffer holds (NE * max_events: each noted step fills an output slot)
+    // ---- balanced bulk rounds (ivp_balance.h; balanced_chunk_kernel_t in rk_global.h) ----
+    uint32_t balance;         // != 0: launch l of the L launches of a balanced round of R attempts, R << 16 | L << 8 | l
+                              // (ivp_balance_pack); `chunk` then carries the plan's quota q, and the input list and its count stay
+                              // the same for all L launches.  0 = every other launch.  (One packed word: it fills what was the
+                              // block's tail padding, so the block and every mirror of its layout keep their size.)
 };
 #define IVP_LOG_SLOTS 32u
 /* doubles before a page's first column group: page header + column headers, rounded up to a whole 128-byte line so that every

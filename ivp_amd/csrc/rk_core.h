@@ -1167,18 +1167,19 @@ IVP_HD void so_log_open(const IvpKArgs &a, uint32_t j, Lane<N, P> &L, uint32_t s
 // together with the same attempt index `it`.  An attempt records at most once in the log-only flavour (FULL == 2:
 // so_log_accepted) and at most twice in the full one (first_step enforcement, solout.rs:392-421), so a page of
 // IVP_LOG_SLOTS slots lasts 32 / 16 attempts.
-template <class MAP, int FULL, int N, int P>
-IVP_HD void so_log_attempt(const IvpKArgs &a, uint32_t j, Lane<N, P> &L, uint32_t it)
+// PIECE: the caller's loop runs `piece` attempts at most (a piece of a balanced round, ivp_balance.h) instead of a.chunk
+template <class MAP, int FULL, bool PIECE = false, int N, int P>
+IVP_HD void so_log_attempt(const IvpKArgs &a, uint32_t j, Lane<N, P> &L, uint32_t it, uint32_t piece = 0)
 {
     constexpr uint32_t kPerAttempt = FULL == 2 ? 1u : 2u, kAttempts = IVP_LOG_SLOTS / kPerAttempt;
     const uint32_t q = it & (kAttempts - 1u);
     if (q == 0u) {
         // pages per allocation: what this launch can use (a.chunk attempts), at most four (a wave that retires early leaves
         // the rest of its arena unopened)
-        const uint32_t want = (a.chunk + kAttempts - 1u) / kAttempts;
+        const uint32_t want = ((PIECE ? piece : a.chunk) + kAttempts - 1u) / kAttempts;
         // (a launch shorter than a page -- chunk_attempts < 32 -- opens pages of just the slots it can use; arenas of more than
         // one page exist only for launches of more than a page, whose pages all have IVP_LOG_SLOTS slots: the gather relies on it)
-        const uint32_t slots = want >= 2u ? IVP_LOG_SLOTS : (a.chunk * kPerAttempt < IVP_LOG_SLOTS ? a.chunk * kPerAttempt : IVP_LOG_SLOTS);
+        const uint32_t slots = want >= 2u ? IVP_LOG_SLOTS : ((PIECE ? piece : a.chunk) * kPerAttempt < IVP_LOG_SLOTS ? (PIECE ? piece : a.chunk) * kPerAttempt : IVP_LOG_SLOTS);
         so_log_open<MAP>(a, j, L, slots, it / kAttempts, want >= 4u ? 4u : (want >= 2u ? 2u : 1u));
     }
     L.log_slot = q * kPerAttempt;
@@ -2665,9 +2666,10 @@ IVP_HD bool rk4_attempt(const IvpKArgs &a, uint32_t j, Lane<R::N, R::P> &L)
     return true;
 }
 
-// One chunk of step attempts for one lane. Every lane leaves after at most `chunk` attempts.
-template <int M, class R, int FULL, bool CTL = false>
-IVP_HD uint32_t chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out)
+// One chunk of step attempts for one lane. Every lane leaves after at most `chunk` attempts (PIECE: after at most `piece`
+// attempts -- a piece of a balanced round, ivp_balance.h).
+template <int M, class R, int FULL, bool CTL = false, bool PIECE = false>
+IVP_HD uint32_t chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out, uint32_t piece = 0)
 {
     Lane<R::N, R::P> L;
     lane_load<R>(a, j, L, M == M_RK23 || M == M_RK4, FULL);
@@ -2681,8 +2683,8 @@ IVP_HD uint32_t chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_out)
     if constexpr (HasInbandOde<R>::v) { L.inb_seed = R::inband_seed(L.p); L.inb_plain = false; }
     uint32_t it = 0;
     bool run = true;
-    while (run && it < a.chunk) {
-        if ((FULL == 1 || FULL == 2) && a.log_pool != nullptr) so_log_attempt<typename OutMap<R>::type, FULL>(a, j, L, it);
+    while (run && it < (PIECE ? piece : a.chunk)) {
+        if ((FULL == 1 || FULL == 2) && a.log_pool != nullptr) so_log_attempt<typename OutMap<R>::type, FULL, PIECE>(a, j, L, it, piece);
         if constexpr (M == M_DOPRI5) run = dopri5_attempt<R, FULL, CTL>(a, j, L);
         else if constexpr (M == M_DOP853) run = dop853_attempt<R, FULL, CTL>(a, j, L);
         else if constexpr (M == M_RK4) run = rk4_attempt<R, FULL>(a, j, L);

@@ -115,3 +115,58 @@ __global__ __launch_bounds__(IVP_WAVE, (M == M_BDF) ? IVP_BDF_MIN_WAVES : ((M ==
 }
 
 }  // namespace IVP_NS
+
+#ifndef __HIPCC_RTC__   // ahead-of-time kernels only
+#include "ivp_balance.h"
+namespace IVP_NS {
+
+// Balanced bulk round (ivp_balance.h): launch l of L.  Workgroup w owns segment w L + l of the round's work line -- q
+// attempts, which fall on one block of 64 list entries or on the end of one and the start of the next -- and runs its
+// pieces one after the other through ONE instance of the attempt body.  The input list and its count are the same for all L
+// launches; a block's last piece of the round appends its survivors to the round's output list, earlier pieces append
+// nothing (a trajectory that retired in an earlier piece is no longer IVP_RUNNING when the last one looks).  No block is
+// touched by two workgroups of one launch, so there is nothing to wait for.
+template <int M, class R, int FULL>
+__global__ __launch_bounds__(IVP_WAVE, IVP_MIN_WAVES) void balanced_chunk_kernel_t(const IvpKArgs a)
+{
+    const uint32_t count = a.perm_in ? *a.count_in : a.B;
+    if (a.count_next && blockIdx.x == 0 && threadIdx.x == 0) *a.count_next = 0u;
+    const uint32_t Rr = ivp_balance_R(a.balance), L = ivp_balance_L(a.balance), l = ivp_balance_l(a.balance), q = a.chunk;
+    const uint32_t nb = (count + (uint32_t)IVP_WAVE - 1u) / (uint32_t)IVP_WAVE;
+    if (Rr == 0u || L == 0u || q == 0u) return;   // not a balanced launch
+    const uint64_t total = (uint64_t)nb * Rr;
+    uint64_t u = ((uint64_t)blockIdx.x * L + l) * q;
+    const uint64_t uend = u + q < total ? u + q : total;
+#pragma unroll 1
+    while (u < uend) {
+        const uint32_t b = (uint32_t)(u / Rr);
+        const uint64_t bend = (uint64_t)(b + 1u) * Rr;
+        const uint32_t n = (uint32_t)((uend < bend ? uend : bend) - u);
+        const bool last = ivp_balance_last_launch(b, Rr, q, L) == l;
+        u += n;
+        const uint32_t i = b * (uint32_t)IVP_WAVE + threadIdx.x;
+        uint32_t j = 0;
+        bool active = false;
+        if (i < count) {
+            j = a.perm_in ? a.perm_in[i] : i;
+            active = a.status[j] == IVP_RUNNING;
+        }
+        uint32_t it = 0;
+        int32_t st = 0;
+        if (active) it = any_chunk_body<M, R, FULL>(a, j, st, n);
+        if (last) compact_append(a, j, active && st == IVP_RUNNING);
+        if (a.slot_counter) {   // as in chunk_kernel_body: a block has at most one piece per launch
+            uint32_t mx = it;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+            const unsigned long long act = __ballot(active);
+            if (lane_id() == 0) {
+                atomicAdd(a.slot_counter, (unsigned long long)mx * IVP_WAVE);
+                atomicAdd(a.slot_counter + 1, (unsigned long long)__popcll(act));
+            }
+        }
+    }
+}
+
+}  // namespace IVP_NS
+#endif

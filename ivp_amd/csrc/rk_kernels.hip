@@ -51,6 +51,14 @@ hipError_t launch_one(int what, const IvpKArgs &a, uint32_t lanes, hipStream_t s
         hipLaunchKernelGGL((init_kernel_t<M, R, FULL>), grid, block, 0, s, a);
         return hipGetLastError();
     }
+    if (what == IVP_LAUNCH_BALANCED) {   // what windows serve (ivp_has_balanced, rk_launch.h): grid = the plan's workgroups
+        if constexpr ((M == M_DOPRI5 || M == M_DOP853) && (FULL == 0 || FULL == 2) && R::N >= 4 && R::NE == 0) {
+            if (a.has_ctl || a.balance == 0u) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((balanced_chunk_kernel_t<M, R, FULL>), grid, block, 0, s, a);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    }
     // a direct method call with its own controller fields (IvpKArgs.has_ctl) runs the CTL = true instantiation;
     // only the lean builds carry it (the host never selects the resident-coefficient variant for such a call)
     constexpr bool kHasCtl = !IVP_HOIST && (M == M_RK23 || M == M_DOPRI5 || M == M_DOP853);

@@ -10,7 +10,16 @@ static inline int ivp_group_width(int n) { return n <= 16 ? 16 : (n <= 32 ? 32 :
 enum { IVP_LAUNCH_INIT = 0, IVP_LAUNCH_CHUNK = 1, IVP_LAUNCH_COOP = 2 /* hiprtc modules only */,
        IVP_LAUNCH_SAMPLE = 3 /* flavour 3's second kernel: one lane per noted step (rk_global.h sample_kernel_t; lean builds, DOP853) */,
        IVP_LAUNCH_EVENTS = 4 /* deferred event refinement: one lane per noted step (rk_global.h event_kernel_t; problems with event functions,
-                                flavour 1, explicit methods, IvpKArgs.evd_rec != NULL) */ };
+                                flavour 1, explicit methods, IvpKArgs.evd_rec != NULL) */,
+       IVP_LAUNCH_BALANCED = 5 /* one launch of a balanced bulk round (ivp_balance.h; rk_global.h balanced_chunk_kernel_t): `lanes` = 64 x
+                                  the plan's workgroups; DOPRI5 / DOP853, flavours 0 and 2, built-in problems of four or more components
+                                  without event functions, compiled-in controller fields -- see ivp_has_balanced() */ };
+
+// whether ivp_launch_strict / _fast / _strict_hoist / _fast_hoist carry a balanced kernel for this solve (methods: ivp_hip.h numbering)
+static inline bool ivp_has_balanced(int method, int rhs_id, int full, int has_ctl)
+{
+    return (method == 1 || method == 2) && (full == 0 || full == 2) && !has_ctl && rhs_id == 3;   // CR3BP: the built-in problem with n >= 4
+}
 
 // `lanes` = upper bound of trajectories the launch has to cover (grid = ceil(lanes / 64) one-wave blocks).
 // `full` = flavour of the kernel: 0 end state only, 1 the whole device DefaultSolOut, 2 log-only (every accepted step recorded,
