@@ -4,6 +4,8 @@ The batches and reference helpers are those of tests/test_failure_paths_cpu.py, 
 oracle, to take the branch it is named after.  The bar is DESIGN section 5's and nothing else: strict GPU == liboracle_detpow
 and FMA GPU == liboracle_fma bit for bit (NaN equal to NaN, as assert_bitexact has it) for y_end, t_end, h_next, status and
 every counter of every trajectory -- the failing ones and their neighbours in the same wavefront.  No tolerance anywhere.
+(For the thread-per-trajectory BDF kernel the neighbours share a batch, not a wavefront: below cus + 1 trajectories the
+launch loop gives every trajectory a wavefront of its own.  tests/test_gpu_wave_density.py runs BDF with 2 .. 64 per wave.)
 
   1. one mixed batch per kernel shape: thread-per-trajectory (rk_core.h / bdf_core.h), lane-cooperative (rk_coop.h),
      wave-per-trajectory explicit (rk_group.h) and wave-per-trajectory BDF (bdf_group.h), each at chunk 0 and an odd chunk;

@@ -91,12 +91,15 @@ OPT = Options(rtol=RT, atol=AT)
 
 
 # ---- 1. one wave plus a tail ------------------------------------------------------------------------------------------
+# (of trajectories, not of lanes: the launch loop spreads a batch this small over the CUs, ONE trajectory per wavefront --
+# lpw = ceil(67 / cus) = 1 on an MI355X -- so neither this test nor any other in this file has two trajectories in one
+# wavefront.  tests/test_gpu_wave_density.py runs these inputs with 2, 7 and 64 trajectories per wavefront.)
 
 def test_one_wave_plus_a_tail_of_stiff_van_der_pol():
     y0, eps = vdp_eps_batch()
     models = vdp_eps_models(67)
     assert any(m.n_reuse > 0 for m in models) and any(m.nrejct > 0 for m in models)
-    assert len({tuple(m.newton_counts[:40]) for m in models}) > 1   # Newton iteration counts diverge inside the wave
+    assert len({tuple(m.newton_counts[:40]) for m in models}) > 1   # Newton iteration counts differ between the trajectories
     r = Radau().solve_batch(ivp_amd.StiffVanDerPol(), 0.0, 2.0, y0, eps, OPT)
     assert_rows(r, models, "stiff VdP, B = 67")
     assert all(m.status == 0 for m in models)
@@ -360,6 +363,9 @@ def test_finite_time_blow_up_ends_in_the_models_status():
 
 
 def test_nan_right_hand_side_in_one_lane_leaves_the_other_63_untouched():
+    """At B = 64 the device runs one trajectory per wavefront (lpw = ceil(64 / cus) = 1), so the 63 are the NaN trajectory's
+    neighbours in the batch and in the state arrays, not in its wavefront; tests/test_gpu_wave_density.py (radau_mixed) puts
+    a NaN right-hand side into a full wavefront."""
     rng = np.random.default_rng(64)
     eps = np.exp(rng.uniform(np.log(2e-2), np.log(5e-2), 64))[None, :]
     y0 = np.stack([2.0 + 0.1 * rng.standard_normal(64), 0.1 * rng.standard_normal(64)])

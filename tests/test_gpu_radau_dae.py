@@ -150,7 +150,9 @@ def test_n1_algebraic_equation_batch_of_1():
 
 @pytest.mark.parametrize("chunk", [0, 1])
 def test_n1_a_mass_per_trajectory_65_trajectories(chunk):
-    """a second wavefront with one live lane; chunk_attempts = 1 puts a launch boundary after every attempt"""
+    """65 trajectories: the batch is one trajectory longer than a wavefront is wide, but at this size the device runs one
+    trajectory per wavefront (lpw = ceil(65 / cus) = 1); tests/test_gpu_wave_density.py (dae_n1_mass_per_trajectory) runs it
+    with full wavefronts.  chunk_attempts = 1 puts a launch boundary after every attempt"""
     p0 = [0.0 if b % 13 == 0 else 0.25 + 0.125 * b for b in range(65)]
     p1 = [1.0 + 0.01 * b for b in range(65)]
     ms = models_of([f_scalar(v) for v in p1], [[[v]] for v in p0], [[1.0]] * 65, 0.0, 2.0)
@@ -245,7 +247,9 @@ def test_n5_pendulum_index_3(tol):
 
 def test_half_the_batch_has_the_wrong_partition_and_its_neighbours_are_untouched():
     """One call, the pure-ODE partition (5, 0, 0): right for the trajectories whose last equation is the index-1 form, wrong for
-    those with the index-2 constraint, which end in StepSizeTooSmall"""
+    those with the index-2 constraint, which end in StepSizeTooSmall.  The six are neighbours in the batch; on the device each
+    has a wavefront to itself (lpw = 1 at this batch size).  tests/test_gpu_wave_density.py (dae_n5_wrong_partition)
+    alternates the two kinds inside one wavefront."""
     sel = [0.0, 1.0, 0.0, 1.0, 1.0, 0.0]
     y0s = [pend_y0(0.1 * b) for b in range(6)]
     fs = [D.rhs_pendulum_index2 if s else f_pend_index1 for s in sel]
