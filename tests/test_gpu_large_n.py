@@ -450,3 +450,45 @@ def test_bdf_large_batches_automatic_factor_placement_changes_no_bit(rhs):
     ref = oracle_batch(rhs, y0[:, idx], None if p is None else p[:, idx], t0, t1 if np.ndim(t1) == 0 else t1[idx], **o)
     sub = {k: (v[..., idx] if isinstance(v, np.ndarray) and v.shape and v.shape[-1] == B else v) for k, v in runs[0].items()}
     assert_bitexact(sub, ref, f"{rhs} automatic factor placement: ")
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("chunk", [1, 0])
+def test_bdf_group_singular_newton_matrix_halves_the_step_like_the_oracle(chunk, variant):
+    """`lu_failed` (bdf.rs:373-381) in the group form, with several trajectories per wavefront: n = 9 runs in groups of 16
+    lanes, B = 5 fills one wavefront and leaves a lone group in the next.  y' = p y with its analytic Jacobian p I; the first
+    attempt runs at order 1 with c = h / alpha(1), alpha(1) = (1 - kappa(1)) gamma(1) = 1.185 (bdf.rs:22, 161-172).  With
+    first_step = alpha(1) the quotient is exactly 1, so I - cJ = (1 - p) I is exactly zero for the trajectories with p = 1
+    (0, 1 and 3) while those with p = 2 and p = 0.5 factorise: groups of one wavefront part at the singular branch.
+    (first_step = 1.0 gives c = 1 / 1.185 and no singular matrix: the oracle's nlu then equals the first_step = 0.5 run's.)
+    Every trajectory equals the oracle run with the same fun and jac, bit for bit, counters included."""
+    import ivp_amd
+    from oracle import oracle as O
+    n, B = 9, 5
+    src = """
+__device__ double ode_comp(int i, double t, const double* y, const double* p) { return p[0] * y[i]; }
+__device__ void jac_col(int col, double t, const double* y, double* column, const double* p) { column[col] = p[0]; }
+"""
+
+    def fun(t, y, p):
+        return [float(p[0]) * float(y[i]) for i in range(n)]
+
+    def jac(t, y, p):
+        return [[float(p[0]) if i == j else 0.0 for j in range(n)] for i in range(n)]
+
+    alpha1 = (1.0 - -0.1850) * 1.0
+    assert alpha1 / alpha1 == 1.0
+    p = np.array([[1.0, 1.0, 2.0, 1.0, 0.5]])
+    y0 = 1.0 + 0.1 * np.arange(n * B, dtype=np.float64).reshape(n, B)
+    o = dict(method="BDF", rtol=1e-6, atol=1e-9)
+    f = ivp_amd.DeviceIVP(src, n=n, params=(1.0,), jac=True)
+    r = ivp_amd.solve_ivp_batch(f, 0.0, 2.0, y0, p, ivp_amd.Options(first_step=alpha1, chunk_attempts=chunk, variant=variant, **o))
+    refs = [O.solve_ivp(fun, 0.0, 2.0, list(y0[:, b]), params=[float(p[0, b])], jac=jac, first_step=alpha1, detpow=True, **o) for b in range(B)]
+    plain = O.solve_ivp(fun, 0.0, 2.0, list(y0[:, 0]), params=[1.0], jac=jac, first_step=0.5, detpow=True, **o)
+    # the singular branch was taken: one factorisation that no Newton iteration followed, counted as a rejection
+    assert refs[0].nlu > plain.nlu and refs[0].nrejct > plain.nrejct
+    for b, s in enumerate(refs):
+        assert int(r.status[b]) == int(s.status) == 0, b
+        got = (int(r.nfev[b]), int(r.njev[b]), int(r.nlu[b]), int(r.naccpt[b]), int(r.nrejct[b]))
+        assert got == (s.nfev, s.njev, s.nlu, s.naccpt, s.nrejct), (b, got)
+        assert np.array_equal(np.asarray(r.y_end)[:, b].view(np.uint64), np.asarray(s.y[-1]).view(np.uint64)), b

@@ -18,6 +18,9 @@ run bdf_fma     rk_bdf.hip -DIVP_FAST=1 &
 run group_strict rk_group.hip -DIVP_FAST=0 &
 run group_fma   rk_group.hip -DIVP_FAST=1 &
 wait
+# the two-waves-per-SIMD BDF build (ivp_amd/csrc/Makefile: *_occ2), whose kernels sit closest to the register limit
+run bdf_occ2_strict rk_bdf.hip -DIVP_FAST=0 -DIVP_BDF_MIN_WAVES=2 -mllvm -disable-machine-licm &
+run bdf_occ2_fma rk_bdf.hip -DIVP_FAST=1 -DIVP_BDF_MIN_WAVES=2 -mllvm -disable-machine-licm &
 run radau_strict rk_radau.hip -DIVP_FAST=0 &
 # the mass-matrix instantiations of the Radau kernels (hiprtc modules only): tools/radau_dae_resources.hip, n = 1, 2, 3, 5, 8
 run radau_dae "$TOOLS/radau_dae_resources.hip" -DIVP_FAST=0 -I. &
