@@ -412,6 +412,24 @@ int ivp_radau_solve_dae_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t
                                const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
                                const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
                                void *hip_stream);
+/*
+ * The direct Radau call in the resumable, the one-pass step log and the CSR dense forms (device pointers).  dae == NULL:
+ * the rules of ivp_radau_solve_device (settings == NULL = the defaults, a problem with a mass matrix is refused); else
+ * those of ivp_radau_solve_dae_device.  Every refusal of those two answers here with the same code and text.
+ *   ivp_radau_submit_device        what ivp_batch_submit_device is to ivp_batch_solve_device; completed by ivp_batch_poll /
+ *                                  ivp_batch_wait.  `settings` and `dae` are read before it returns: they may go out of
+ *                                  scope while the solve is in flight (`out` and the input arrays may not).
+ *   ivp_radau_solve_logged_device  the contract of ivp_batch_solve_logged_device below, member for member (reserve, defer,
+ *                                  caller- or library-owned buffers, passes, pool_bytes, pool_used_bytes, the counted second
+ *                                  integration when the pool runs dry); ivp_step_log_fetch_device / ivp_step_log_free apply.
+ *   ivp_radau_solve_dense_device   the contract of ivp_batch_solve_dense_device below; ncoef_n = 4 n, and
+ *                                  ivp_dense_eval_device(method = IVP_RADAU) evaluates the result.
+ * (The latter two are declared below, behind ivp_step_log_t and ivp_dense_log_t.)
+ */
+int ivp_radau_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                            const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                            void *hip_stream);
 
 /*
  * Solution.t / Solution.y of B solve_ivp() calls in ONE call and ONE integration (ABI v5).
@@ -465,6 +483,11 @@ typedef struct {
 int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0,
                                   const double *params, const double *t0, size_t t0_len, const double *t1,
                                   size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out,
+                                  ivp_step_log_t *log, void *hip_stream);
+/* ... through the direct Radau call (see ivp_radau_submit_device): opt->method is ignored */
+int ivp_radau_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
                                   ivp_step_log_t *log, void *hip_stream);
 /* the records of the context's last logged solve (defer = 1, or after IVP_ERR_LOG_CAPACITY) into log->t / log->y
  * (device memory, `capacity` records; both NULL: allocated here); log->offsets is not touched.  That solve must be the
@@ -522,6 +545,11 @@ typedef struct {
 int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0,
                                  const double *params, const double *t0, size_t t0_len, const double *t1,
                                  size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out,
+                                 ivp_dense_log_t *dense, void *hip_stream);
+/* ... through the direct Radau call (see ivp_radau_submit_device): opt->method is ignored, cont is [c0, c1, c2, c3][component] */
+int ivp_radau_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                 const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
                                  ivp_dense_log_t *dense, void *hip_stream);
 /* host pointers throughout (arguments as ivp_batch_solve; dense->offsets / cont / xold / h are host memory) */
 int ivp_batch_solve_dense(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,

@@ -118,6 +118,7 @@ EXPORTS = (
     "ivp_batch_solve_events_device", "ivp_batch_solve_events", "ivp_event_log_fetch_device", "ivp_event_log_free",
     "ivp_radau_settings_default", "ivp_radau_solve", "ivp_radau_solve_device", "ivp_options_check", "ivp_radau_check",
     "ivp_radau_dae_check", "ivp_radau_solve_dae", "ivp_radau_solve_dae_device",
+    "ivp_radau_submit_device", "ivp_radau_solve_logged_device", "ivp_radau_solve_dense_device",
 )
 
 ERRORS = {
@@ -203,6 +204,14 @@ def load():
     L.ivp_radau_solve_dae.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT), solve_args[-1]]
     L.ivp_radau_solve_dae_device.restype = C.c_int
     L.ivp_radau_solve_dae_device.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT), solve_args[-1], C.c_void_p]
+    # the resumable, one-pass step log and CSR dense forms of the direct Radau call: `dae` may be NULL (the rules of ivp_radau_solve_device)
+    radau_args = solve_args[:-1] + [C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT), solve_args[-1]]
+    L.ivp_radau_submit_device.restype = C.c_int
+    L.ivp_radau_submit_device.argtypes = radau_args + [C.c_void_p]
+    L.ivp_radau_solve_logged_device.restype = C.c_int
+    L.ivp_radau_solve_logged_device.argtypes = radau_args + [C.POINTER(StepLogT), C.c_void_p]
+    L.ivp_radau_solve_dense_device.restype = C.c_int
+    L.ivp_radau_solve_dense_device.argtypes = radau_args + [C.POINTER(DenseLogT), C.c_void_p]
     L.ivp_batch_solve_multi.argtypes = [C.POINTER(ShardT), C.c_int32, C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT),
                                         C.c_int32, C.POINTER(BatchResultT)]
     L.ivp_batch_solve_multi_host.restype = C.c_int

@@ -972,8 +972,8 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
     copt = options._c(n, keep)
     method = options.method_enum
     if _radau is not None:   # the direct Radau call (ivp_amd.Radau): Options.method is ignored
-        if not wait or _steplog is not None or _dense is not None or _events is not None:
-            raise ValueError("Radau: the resumable, one-pass log, CSR dense and CSR event forms are not on its path yet")
+        if _events is not None:
+            raise ValueError("Radau: the CSR event form is not on its path (Radau has no events yet)")
         method = Method.RADAU
     per_traj = options.t_eval_per_trajectory is not None
     if per_traj:
@@ -1084,13 +1084,18 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
     for name, _ in _lib.BatchResultT._fields_:
         setattr(r, name, ptr(getattr(res, name)))
     prob = _problem_c(f)
+    dae_ref = None if _radau_dae is None else C.byref(_radau_dae)   # NULL: the rules of ivp_radau_solve_device
     if not wait:
         if not on_device:
             raise ValueError("wait=False needs device arrays (the host-pointer entry point copies results back at the end)")
         import torch
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
-        rc = ctx.lib.ivp_batch_submit_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
-                                             ptr(t1a), t1_len, C.byref(copt), C.byref(r), stream)
+        if _radau is not None:   # ivp_amd.Radau: the library copies what it needs of the two structs before it returns
+            rc = ctx.lib.ivp_radau_submit_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len, ptr(t1a), t1_len,
+                                                 C.byref(copt), C.byref(_radau), dae_ref, C.byref(r), stream)
+        else:
+            rc = ctx.lib.ivp_batch_submit_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                 ptr(t1a), t1_len, C.byref(copt), C.byref(r), stream)
         if rc != 0:
             raise ConfigError(rc, ctx.last_error())
         return PendingBatch(ctx, res, bool(options.profile), keep + [y0, params, t0a, t1a, copt, r])
@@ -1099,8 +1104,12 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         if not on_device:
             raise ValueError("the CSR dense log takes device arrays")
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
-        rc = ctx.lib.ivp_batch_solve_dense_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
-                                                  ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_dense), stream)
+        if _radau is not None:
+            rc = ctx.lib.ivp_radau_solve_dense_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len, ptr(t1a), t1_len,
+                                                      C.byref(copt), C.byref(_radau), dae_ref, C.byref(r), C.byref(_dense), stream)
+        else:
+            rc = ctx.lib.ivp_batch_solve_dense_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                      ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_dense), stream)
     elif _events is not None:   # solve_ivp_batch_events: counting solve + scan + the occurrences as a CSR log
         import torch
         if not on_device:
@@ -1113,8 +1122,12 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         if not on_device:
             raise ValueError("the one-pass step log takes device arrays")
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
-        rc = ctx.lib.ivp_batch_solve_logged_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
-                                                   ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_steplog), stream)
+        if _radau is not None:
+            rc = ctx.lib.ivp_radau_solve_logged_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len, ptr(t1a), t1_len,
+                                                       C.byref(copt), C.byref(_radau), dae_ref, C.byref(r), C.byref(_steplog), stream)
+        else:
+            rc = ctx.lib.ivp_batch_solve_logged_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                       ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_steplog), stream)
         if rc == -105:   # IVP_ERR_LOG_CAPACITY: the integration is complete, the records wait in the pool for larger buffers
             rc = 0
     elif _radau is not None and _radau_dae is not None:   # M y' = f / DAE index sets (ivp_amd.Radau): a _lib.RadauDaeT
@@ -1152,7 +1165,7 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
 
 
 def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                           out: BatchSolution = None, reserve: int = 0, two_pass: bool = False) -> BatchSolution:
+                           out: BatchSolution = None, reserve: int = 0, two_pass: bool = False, _radau=None, _radau_dae=None) -> BatchSolution:
     """``Solution.t`` / ``Solution.y`` of B independent solves -- every accepted step of every trajectory -- in CSR form,
     from ONE integration (``ivp_batch_solve_logged_device``).
 
@@ -1180,8 +1193,9 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
     n, B = int(y0d.shape[0]), int(y0d.shape[1])
     base = {k: v for k, v in options.__dict__.items() if k not in ("max_log", "count_log", "profile")}
     ml = options.max_log if options.dense_output else 0
+    rad = dict(_radau=_radau, _radau_dae=_radau_dae)   # ivp_amd.Radau.solve_batch_logged: every solve below is the direct Radau call
     if two_pass:
-        cnt = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**base, max_log=ml, count_log=True), ctx)
+        cnt = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**base, max_log=ml, count_log=True), ctx, **rad)
         offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
         torch.cumsum(cnt.n_log.to(torch.int64), 0, out=offsets[1:])
         total = int(offsets[-1].item())
@@ -1189,7 +1203,7 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
                            nrejct=cnt.nrejct, h_next=cnt.h_next, njev=cnt.njev, nlu=cnt.nlu, n_log=cnt.n_log,
                            t_log=torch.empty(max(total, 1), dtype=torch.float64, device=dev),
                            y_log=torch.empty((max(total, 1), n), dtype=torch.float64, device=dev), log_offsets=offsets)
-        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**base, max_log=ml, profile=options.profile), ctx, o2)
+        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**base, max_log=ml, profile=options.profile), ctx, o2, **rad)
         res.t_log, res.y_log = res.t_log[:total], res.y_log[:total]
         res.log_info = {"passes": 2, "form": "counting solve + scan + filling solve"}
         return res
@@ -1218,7 +1232,7 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
     if o1.n_log is None:
         o1.n_log = torch.zeros(B, dtype=torch.int32, device=dev)
     opts1 = Options(**base, max_log=ml, profile=options.profile)
-    res = solve_ivp_batch(f, t0d, t1d, y0d, pd, opts1, ctx, o1, _steplog=sl)
+    res = solve_ivp_batch(f, t0d, t1d, y0d, pd, opts1, ctx, o1, _steplog=sl, **rad)
     total = int(sl.total)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     if bufs is None or sl.capacity < total:
@@ -1233,7 +1247,7 @@ def solve_ivp_batch_logged(f: IVP, t0, t1, y0, params=None, options: Options = N
             if rc != -100 or "pool ran dry" not in err:
                 raise ConfigError(rc, err)
             sl.reserve = 0   # automatic: the pool's size now follows the counted total (what the first attempt asked of its fullest sub-pool)
-            res = solve_ivp_batch(f, t0d, t1d, y0d, pd, opts1, ctx, o1, _steplog=sl)
+            res = solve_ivp_batch(f, t0d, t1d, y0d, pd, opts1, ctx, o1, _steplog=sl, **rad)
             sl.passes += 1
     res.log_offsets = offsets
     res._log_buffers = bufs
@@ -1316,7 +1330,8 @@ class BatchContinuousOutput:
         return y, found
 
 
-def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None) -> BatchSolution:
+def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
+                          _radau=None, _radau_dae=None) -> BatchSolution:
     """B independent ``solve_ivp(.., Options(dense_output=True))`` calls with EVERY trajectory's complete ContinuousOutput
     (src/solve/cont.rs:9-153), not capped at ``max_log``: the segments come back as a CSR log on the device.
 
@@ -1344,7 +1359,8 @@ def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = No
     offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
     dl.offsets = offsets.data_ptr()
     try:
-        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**{**options.__dict__, "dense_output": True}), ctx, _dense=dl)
+        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, Options(**{**options.__dict__, "dense_output": True}), ctx, _dense=dl,
+                              _radau=_radau, _radau_dae=_radau_dae)
         total, nc = int(dl.total), int(dl.ncoef_n)
         cont = torch.empty((max(total, 1), nc), dtype=torch.float64, device=dev)
         xold = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
@@ -1358,7 +1374,7 @@ def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = No
     res.seg_offsets = offsets
     res.seg_cont, res.seg_xold, res.seg_h = cont[:total], xold[:total], h[:total]
     res.dense_info = {"passes": int(dl.passes), "segments": total, "bytes": total * (nc + 2) * 8, "staging_bytes": int(dl.staging_bytes)}
-    res.dense = BatchContinuousOutput(options.method_enum, int(y0d.shape[0]), offsets, res.seg_cont, res.seg_xold, res.seg_h, options.fp_mode, ctx)
+    res.dense = BatchContinuousOutput(options.method_enum if _radau is None else Method.RADAU, int(y0d.shape[0]), offsets, res.seg_cont, res.seg_xold, res.seg_h, options.fp_mode, ctx)
     return res
 
 

@@ -653,20 +653,6 @@ int ivp_rhs_n_events(int32_t rhs_id)
 
 namespace {
 
-// RADAU::solve's input validation (radau.rs:132-262) for the fields of ivp_radau_settings_t / ivp_options_t, after the
-// checks every entry point shares; what the Radau path does not cover yet is IVP_ERR_BAD_ARGUMENT.  No device is touched.
-// what the Radau entry points hand down: the public settings, and for ivp_radau_solve_dae*() the resolved DAE partition
-struct RadauCall : ivp_radau_settings_t {
-    int dae_call = 0;                    // ivp_radau_solve_dae*(): a problem with a mass matrix is accepted
-    const ivp_radau_dae_t *dae = nullptr;
-    int nind2 = 0, nind3 = 0;            // set by radau_validate
-    RadauCall(const ivp_radau_settings_t *s, int dae_call_, const ivp_radau_dae_t *dae_) : dae_call(dae_call_), dae(dae_)
-    {
-        if (s) *static_cast<ivp_radau_settings_t *>(this) = *s;
-        else ivp_radau_settings_default(this);
-    }
-};
-
 // the DAE partition, by the reference's rules and in its order (radau.rs:210-246); the counts are usize there, so a negative
 // one cannot be expressed: it gets the same error
 int radau_partition(ivp_ctx *ctx, int n, const ivp_radau_dae_t *dae, int *nind2_out, int *nind3_out)
@@ -692,7 +678,11 @@ int radau_partition(ivp_ctx *ctx, int n, const ivp_radau_dae_t *dae, int *nind2_
     return IVP_OK;
 }
 
-int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, RadauCall *rad, int *n_out, int *p_out)
+}  // namespace
+
+// RADAU::solve's input validation (radau.rs:132-262) for the fields of ivp_radau_settings_t / ivp_options_t, after the
+// checks every entry point shares; what the Radau path does not cover yet is IVP_ERR_BAD_ARGUMENT.  No device is touched.
+int ivp_host::radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, RadauCall *rad, int *n_out, int *p_out)
 {
     const int rc = validate(ctx, prob, B, opt, n_out, p_out, rad->dae_call ? IVP_VALIDATE_RADAU_DAE : IVP_VALIDATE_RADAU);
     if (rc != IVP_OK) return rc;
@@ -724,6 +714,8 @@ int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_
     if (opt->has_first_step && opt->first_step == 0.0) return fail(ctx, IVP_ERR_INVALID_STEP_SIZE, "Radau: first_step is zero");
     return IVP_OK;
 }
+
+namespace {
 
 int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
@@ -1234,6 +1226,14 @@ int ivp_radau_solve_dae_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t
     return ivp_batch_wait(ctx);
 }
 
+int ivp_radau_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                            const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out, void *hip_stream)
+{
+    RadauCall call = radau_call(settings, dae);   // read here and now: the context keeps what the later rounds need
+    return submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, &call);
+}
+
 int ivp_batch_poll(ivp_ctx_t *ctx, int *done)
 {
     if (!ctx || !done) return IVP_ERR_BAD_ARGUMENT;
@@ -1270,6 +1270,18 @@ int ivp_batch_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
     if (rc != IVP_OK) return rc;
     return ivp_batch_wait(ctx);
 }
+
+}  // extern "C"
+
+int ivp_host::solve_device(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
+                           const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, void *hip_stream, RadauCall *rad)
+{
+    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, rad);
+    if (rc != IVP_OK) return rc;
+    return ivp_batch_wait(ctx);
+}
+
+extern "C" {
 
 int ivp_batch_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                     const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,

@@ -154,10 +154,32 @@ hipError_t copy_rows(void *dst, size_t dst_stride, const void *src, size_t src_s
 hipError_t copy_rows_peer(void *dst, int dst_dev, size_t dst_stride, const void *src, int src_dev, size_t src_stride, size_t elem,
                           size_t count, size_t rows, hipStream_t s);
 // Options / problem validation shared by every entry point (ivp_capi.cpp)
-// (radau: the call comes from ivp_radau_solve*(), the only entry points that integrate with IVP_RADAU)
-// ... IVP_VALIDATE_RADAU_DAE: ivp_radau_solve_dae*(), the only entry points that accept a problem with a mass matrix)
+// (radau: the call comes from ivp_radau_*(), the only entry points that integrate with IVP_RADAU)
+// ... IVP_VALIDATE_RADAU_DAE: ivp_radau_solve_dae*() and the ivp_radau_*_device forms given a partition, the only entry points
+// that accept a problem with a mass matrix)
 enum { IVP_VALIDATE_SOLVE_IVP = 0, IVP_VALIDATE_RADAU = 1, IVP_VALIDATE_RADAU_DAE = 2 };
 int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, int *n_out, int *p_out, int radau = IVP_VALIDATE_SOLVE_IVP);
+// what the Radau entry points hand down: the public settings, and for the DAE calls the resolved partition.  submit_impl
+// lays everything the kernels read into the argument block the context keeps (Pending::a), so neither this object nor the
+// caller's structs are looked at once the submit has returned.
+struct RadauCall : ivp_radau_settings_t {
+    int dae_call = 0;                    // ivp_radau_solve_dae*(): a problem with a mass matrix is accepted
+    const ivp_radau_dae_t *dae = nullptr;
+    int nind2 = 0, nind3 = 0;            // set by radau_validate
+    RadauCall(const ivp_radau_settings_t *s, int dae_call_, const ivp_radau_dae_t *dae_) : dae_call(dae_call_), dae(dae_)
+    {
+        if (s) *static_cast<ivp_radau_settings_t *>(this) = *s;
+        else ivp_radau_settings_default(this);
+    }
+};
+// the call of ivp_radau_{submit,solve_logged,solve_dense}_device: dae == NULL follows the rules of ivp_radau_solve_device
+// (default settings for NULL, a mass matrix refused), anything else those of ivp_radau_solve_dae_device
+inline RadauCall radau_call(const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae) { return RadauCall(settings, dae ? 1 : 0, dae); }
+int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, RadauCall *rad, int *n_out, int *p_out);
+// ivp_batch_solve_device, or -- rad != NULL -- the blocking direct Radau solve (opt->method is ignored): the ONE solve the
+// step-log and dense-log drivers (ivp_log.cpp, ivp_dense.cpp) run, as often as they need it
+int solve_device(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
+                 const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, void *hip_stream, RadauCall *rad);
 // restores the caller's current HIP device when a multi-device entry point returns
 struct DeviceGuard {
     int dev = -1;

@@ -87,7 +87,7 @@ int device_destination(ivp_ctx *ctx, ivp_dense_log_t *d, uint64_t total, size_t 
 // device arrays of the whole batch (SoA stride B); off: device offsets [B + 1]; ns: the counts on the host.
 int fill_pass(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
               const double *t1, size_t t1_len, const ivp_options_t *opt, int n, int np, size_t nc, const std::vector<uint32_t> &ns,
-              const unsigned long long *off, ivp_dense_log_t *d, uint32_t *err, hipStream_t s)
+              const unsigned long long *off, ivp_dense_log_t *d, uint32_t *err, hipStream_t s, RadauCall *rad = nullptr)
 {
     const size_t rec = (nc + 2) * sizeof(double);
     size_t fr = 0, tot = 0;
@@ -139,7 +139,7 @@ int fill_pass(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y
         r.seg_h = r.seg_xold + (size_t)ml * cnt;
         r.n_seg = (uint32_t *)cnt_buf.p;
         o.max_log = ml;
-        int rc = ivp_batch_solve_device(ctx, prob, cnt, ys, ps, t0s, t0_len == 1 ? 1 : cnt, t1s, t1_len == 1 ? 1 : cnt, &o, &r, s);
+        int rc = solve_device(ctx, prob, cnt, ys, ps, t0s, t0_len == 1 ? 1 : cnt, t1s, t1_len == 1 ? 1 : cnt, &o, &r, s, rad);
         if (rc != IVP_OK) return rc;
         DensePackArgs p{r.seg_cont, r.seg_xold, r.seg_h, r.n_seg, off + first, d->cont, d->xold, d->h, err, (uint32_t)cnt, ml, (uint32_t)nc};
         HIP_TRY(ctx, ivp_dense_pack(p, s));
@@ -168,20 +168,25 @@ int check_args(ivp_ctx *ctx, const ivp_options_t *opt, const ivp_batch_result_t 
     return IVP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
-                                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
-                                 ivp_batch_result_t *out, ivp_dense_log_t *dense, void *hip_stream)
+// the dense solve on device pointers; rad: the direct Radau call (ivp_radau_solve_dense_device: opt->method is ignored, the
+// segments are Radau's), NULL otherwise -- it is handed to the counting solve and to every filling solve
+int dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                 ivp_batch_result_t *out, ivp_dense_log_t *dense, void *hip_stream, RadauCall *rad)
 {
     if (!ctx) return IVP_ERR_BAD_ARGUMENT;
     ctx->err.clear();
     int rc = check_args(ctx, opt, out, dense);
     if (rc != IVP_OK) return rc;
     int n = 0, np = 0;
-    rc = validate(ctx, prob, B, opt, &n, &np);
+    ivp_options_t radau_opt;
+    if (rad) {   // as submit_impl reads them
+        radau_opt = *opt;
+        radau_opt.method = IVP_RADAU;
+        radau_opt.has_settings = 0;
+        opt = &radau_opt;
+    }
+    rc = rad ? radau_validate(ctx, prob, B, opt, rad, &n, &np) : validate(ctx, prob, B, opt, &n, &np);
     if (rc != IVP_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)hip_stream;
@@ -206,7 +211,7 @@ int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size
     const bool alias = out->y_end != nullptr && (const double *)out->y_end == y0;   // the filling solve needs y0 intact
     if (alias) { HIP_TRY(ctx, yend.get(sizeof(double) * n * B)); r.y_end = (double *)yend.p; }
     dense->staging_bytes = stage1;
-    rc = ivp_batch_solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream);
+    rc = solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream, rad);
     if (rc != IVP_OK) return rc;
     const ivp_run_stats_t stats = ctx->stats;   // what the caller's options asked for describes the counting solve
     dense->passes = 1;
@@ -236,13 +241,33 @@ int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size
     } else {
         st.release();
         rc = fill_pass(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, n, np, nc, ns, (const unsigned long long *)dense->offsets, dense,
-                       (uint32_t *)err.p, s);
+                       (uint32_t *)err.p, s, rad);
         ctx->stats = stats;
         if (rc != IVP_OK) return rc;
         dense->passes = 2;
     }
     if (alias) HIP_TRY(ctx, hipMemcpyAsync(out->y_end, yend.p, sizeof(double) * n * B, hipMemcpyDeviceToDevice, s));
     return check_err(ctx, (const uint32_t *)err.p, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivp_batch_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                 ivp_batch_result_t *out, ivp_dense_log_t *dense, void *hip_stream)
+{
+    return dense_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, dense, hip_stream, nullptr);
+}
+
+int ivp_radau_solve_dense_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                 const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                 const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                                 ivp_dense_log_t *dense, void *hip_stream)
+{
+    RadauCall call = radau_call(settings, dae);
+    return dense_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, dense, hip_stream, &call);
 }
 
 int ivp_batch_solve_dense(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,

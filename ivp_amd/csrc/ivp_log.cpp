@@ -111,13 +111,11 @@ int gather_pool(ivp_ctx *ctx, const unsigned long long *offsets_dev, uint64_t ca
     return IVP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
-                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
-                                  ivp_batch_result_t *out, ivp_step_log_t *log, void *hip_stream)
+// the logged solve on device pointers; rad: the direct Radau call (ivp_radau_solve_logged_device), NULL otherwise -- it is
+// handed to every integration this driver runs (the recording one, and the counted fill pass after a pool that ran dry)
+int logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                  ivp_batch_result_t *out, ivp_step_log_t *log, void *hip_stream, RadauCall *rad)
 {
     if (!ctx) return IVP_ERR_BAD_ARGUMENT;
     if (!opt || !out || !log || !log->offsets) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null options / out / log / log->offsets");
@@ -130,7 +128,7 @@ int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, siz
     r.t_log = nullptr; r.y_log = nullptr; r.log_offsets = nullptr;
     ctx->log_plan.want = true;
     ctx->log_plan.reserve = log->reserve;
-    int rc = ivp_batch_solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream);
+    int rc = solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream, rad);
     ctx->log_plan = ivp_ctx::LogPlan{};
     if (rc != IVP_OK) return rc;
     log->passes = 1;
@@ -159,10 +157,30 @@ int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, siz
     }
     // the pool ran dry: the counts are exact, so this is the counted two-pass log whose first pass has just been done
     r.t_log = log->t; r.y_log = log->y; r.log_offsets = log->offsets;
-    rc = ivp_batch_solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream);
+    rc = solve_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, &o, &r, hip_stream, rad);
     if (rc != IVP_OK) return rc;
     log->passes = 2;
     return IVP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivp_batch_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  ivp_batch_result_t *out, ivp_step_log_t *log, void *hip_stream)
+{
+    return logged_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, log, hip_stream, nullptr);
+}
+
+int ivp_radau_solve_logged_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                                  ivp_step_log_t *log, void *hip_stream)
+{
+    RadauCall call = radau_call(settings, dae);
+    return logged_device(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, log, hip_stream, &call);
 }
 
 int ivp_step_log_fetch_device(ivp_ctx_t *ctx, ivp_step_log_t *log, void *hip_stream)

@@ -31,10 +31,11 @@ class BatchPipeline:
 
     def map(self, f: api.IVP, batches: Sequence[dict], options: api.Options,
             on_done: Optional[Callable[[int, api.BatchSolution], None]] = None,
-            out_per_context: Optional[Sequence[api.BatchSolution]] = None) -> List[api.BatchSolution]:
+            out_per_context: Optional[Sequence[api.BatchSolution]] = None, radau=None) -> List[api.BatchSolution]:
         """``batches``: dicts with keys t0, t1, y0, params (CUDA tensors / scalars as for solve_ivp_batch).  Results
         come back in input order.  ``out_per_context``: one reusable BatchSolution per stream (results of different
-        batches then alias: consume them in ``on_done``)."""
+        batches then alias: consume them in ``on_done``).  ``radau``: an ``ivp_amd.Radau`` -- every batch is then its
+        ``solve_batch(..., wait=False)`` (``options.method`` is ignored)."""
         import time
         import torch
         results: List[Optional[api.BatchSolution]] = [None] * len(batches)
@@ -63,8 +64,11 @@ class BatchPipeline:
                         b = batches[nxt]
                         with torch.cuda.stream(self.streams[w]):
                             out = out_per_context[w] if out_per_context is not None else b.get("out")
-                            inflight[w] = (nxt, api.solve_ivp_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options,
-                                                                    self.ctxs[w], out, wait=False))
+                            if radau is not None:
+                                pend = radau.solve_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options, self.ctxs[w], out, wait=False)
+                            else:
+                                pend = api.solve_ivp_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options, self.ctxs[w], out, wait=False)
+                            inflight[w] = (nxt, pend)
                         nxt += 1
                         progressed = True
                 # nothing ready: poll again (a round lasts 0.3-2 ms; each poll is one hipEventQuery per context),
@@ -89,8 +93,8 @@ class BatchPipeline:
         return results  # type: ignore[return-value]
 
     def map_threads(self, f: api.IVP, batches: Sequence[dict], options: api.Options,
-                    on_done: Optional[Callable[[int, api.BatchSolution], None]] = None) -> List[api.BatchSolution]:
-        """One blocking host thread per stream; batch k is integrated by worker k % streams."""
+                    on_done: Optional[Callable[[int, api.BatchSolution], None]] = None, radau=None) -> List[api.BatchSolution]:
+        """One blocking host thread per stream; batch k is integrated by worker k % streams.  ``radau``: as in ``map``."""
         import torch
         results: List[Optional[api.BatchSolution]] = [None] * len(batches)
         errors: List[BaseException] = []
@@ -100,8 +104,11 @@ class BatchPipeline:
                 with torch.cuda.stream(self.streams[w]):
                     for k in range(w, len(batches), len(self.streams)):
                         b = batches[k]
-                        results[k] = api.solve_ivp_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options,
-                                                         self.ctxs[w], b.get("out"))
+                        if radau is not None:
+                            results[k] = radau.solve_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options, self.ctxs[w], b.get("out"))
+                        else:
+                            results[k] = api.solve_ivp_batch(f, b["t0"], b["t1"], b["y0"], b.get("params"), options,
+                                                             self.ctxs[w], b.get("out"))
                         if on_done is not None:
                             on_done(k, results[k])
             except BaseException as e:  # surfaced to the caller below

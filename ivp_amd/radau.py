@@ -6,7 +6,11 @@ banded storage) or ``Dense64()``, one matrix row per lane with the factors in LD
 ``M y' = f(t, y)`` with a constant, possibly singular mass matrix -- a ``DeviceIVP(..., mass=True)`` -- and index-1/2/3
 algebraic variables (``nind1`` / ``nind2`` / ``nind3``).
 ``solve_ivp(..., Options(method="RADAU"))`` still answers ``IVP_ERR_UNSUPPORTED_METHOD``; this class is the way in, and it
-carries the struct fields ``solve_ivp`` cannot reach.
+carries the struct fields ``solve_ivp`` cannot reach.  Besides the blocking ``solve`` / ``solve_batch`` (bounded ``max_log``
+logs) it has the forms the other methods have for batches whose step counts are not known in advance:
+``solve_batch(..., wait=False)`` (a ``PendingBatch``; ``BatchPipeline.map(..., radau=...)`` overlaps several),
+``solve_batch_logged`` (every accepted step, CSR, one integration) and ``solve_batch_dense`` (every segment, CSR, evaluated on
+the device).  Not there: events in any form, the multi-GPU entry points.
 """
 from typing import Optional, Sequence
 
@@ -61,6 +65,23 @@ class Radau:
         return api.solve_ivp(f, t0, t1, y0, options, ctx, _radau=self._c(), _radau_dae=self._dae(f))
 
     def solve_batch(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None, ctx: api.Context = None,
-                    out: api.BatchSolution = None) -> api.BatchSolution:
-        """B independent ``solve`` calls; host (numpy) or device (torch) arrays, like ``solve_ivp_batch``."""
-        return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, _radau=self._c(), _radau_dae=self._dae(f))
+                    out: api.BatchSolution = None, wait: bool = True):
+        """B independent ``solve`` calls; host (numpy) or device (torch) arrays, like ``solve_ivp_batch``.
+        ``wait=False`` (device arrays only): enqueue the solve (``ivp_radau_submit_device``) and return a ``PendingBatch``."""
+        if not wait and not api._is_torch(y0):
+            raise ValueError("wait=False needs device arrays (the host-pointer entry point copies results back at the end)")
+        return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, wait=wait, _radau=self._c(), _radau_dae=self._dae(f))
+
+    def solve_batch_logged(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None, ctx: api.Context = None,
+                           out: api.BatchSolution = None, reserve: int = 0, two_pass: bool = False) -> api.BatchSolution:
+        """Every accepted step of every trajectory in CSR form from ONE integration (``ivp_radau_solve_logged_device``): the
+        result, ``reserve``, ``out`` and ``two_pass`` of ``solve_ivp_batch_logged``; no ``max_log`` to guess."""
+        return api.solve_ivp_batch_logged(f, t0, t1, y0, params, options, ctx, out=out, reserve=reserve, two_pass=two_pass,
+                                          _radau=self._c(), _radau_dae=self._dae(f))
+
+    def solve_batch_dense(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None,
+                          ctx: api.Context = None) -> api.BatchSolution:
+        """Every trajectory's complete continuous output as a CSR log (``ivp_radau_solve_dense_device``): the result of
+        ``solve_ivp_batch_dense`` with 4 n coefficients per segment; ``result.dense`` is a ``BatchContinuousOutput`` with
+        ``Method.RADAU`` that evaluates y(t) on the device."""
+        return api.solve_ivp_batch_dense(f, t0, t1, y0, params, options, ctx, _radau=self._c(), _radau_dae=self._dae(f))

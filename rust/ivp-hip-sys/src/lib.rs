@@ -285,6 +285,19 @@ extern "C" {
                                       t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
                                       settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
                                       hip_stream: *mut c_void) -> c_int;
+    // ... resumable (ivp_batch_poll / ivp_batch_wait complete it), with the one-pass step log, with the CSR dense log; dae may be null
+    pub fn ivp_radau_submit_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                   t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                   settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                   hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_radau_solve_logged_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                         t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                         settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                         log: *mut ivp_step_log_t, hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_radau_solve_dense_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                        t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                        settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                        dense: *mut ivp_dense_log_t, hip_stream: *mut c_void) -> c_int;
     // Solution.t / Solution.y in ONE call and ONE integration (page pool + gather kernel)
     pub fn ivp_batch_solve_logged_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64,
                                          params: *const f64, t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize,
