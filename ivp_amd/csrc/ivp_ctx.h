@@ -1,6 +1,6 @@
 // ivp_ctx.h -- PRIVATE host-side header of libivp_hip.so: the context object behind ivp_ctx_t and the helpers the
 // translation units of the host library share (ivp_capi.cpp: validation, launch loop, SoA result plumbing; ivp_log.cpp:
-// the one-pass accepted-step log).  Not part of the C ABI (include/ivp_hip.h is).
+// the one-pass accepted-step log; ivp_csr.cpp: the counted dense and event logs).  Not part of the C ABI (include/ivp_hip.h is).
 #pragma once
 #include "../../include/ivp_hip.h"
 
@@ -177,7 +177,7 @@ struct RadauCall : ivp_radau_settings_t {
 inline RadauCall radau_call(const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae) { return RadauCall(settings, dae ? 1 : 0, dae); }
 int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, RadauCall *rad, int *n_out, int *p_out);
 // ivp_batch_solve_device, or -- rad != NULL -- the blocking direct Radau solve (opt->method is ignored): the ONE solve the
-// step-log and dense-log drivers (ivp_log.cpp, ivp_dense.cpp) run, as often as they need it
+// step-log driver (ivp_log.cpp) and the staging driver of the dense and event logs (ivp_csr.cpp) run, as often as they need it
 int solve_device(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
                  const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, void *hip_stream, RadauCall *rad);
 // restores the caller's current HIP device when a multi-device entry point returns

@@ -231,15 +231,16 @@ def test_device_eval_equals_the_host_wide_and_odd_systems(f, method, B, t1):
     _eval_equals_host(d, B, t1 + 1.0)
 
 
-def _host_form(f, y0, p, t0, t1, opts):
-    """ivp_batch_solve_dense (host pointers throughout, library-owned host log)"""
+def _host_form(f, y0, p, t0, t1, opts, alias=False):
+    """ivp_batch_solve_dense (host pointers throughout, library-owned host log); alias: y_end is written over (a private
+    copy of) y0"""
     L, ctx = _lib.load(), ivp_amd.default_context(0)
     keep = []
     copt = opts._c(f.n, keep)
     B = y0.shape[1]
-    y0 = np.ascontiguousarray(y0, dtype=np.float64)
+    y0 = np.array(y0, dtype=np.float64, order="C") if alias else np.ascontiguousarray(y0, dtype=np.float64)
     p = None if p is None else np.ascontiguousarray(p, dtype=np.float64)
-    y_end, n_seg = np.zeros((f.n, B)), np.zeros(B, np.uint32)
+    y_end, n_seg = y0 if alias else np.zeros((f.n, B)), np.zeros(B, np.uint32)
     r = _lib.BatchResultT()
     r.y_end, r.n_seg = y_end.ctypes.data, n_seg.ctypes.data
     off = np.zeros(B + 1, np.uint64)
@@ -253,21 +254,80 @@ def _host_form(f, y0, p, t0, t1, opts):
     total, nc = int(dl.total), int(dl.ncoef_n)
     assert dl.owned == 1 and dl.device == -1 and int(off[-1]) == total
     get = lambda ptr, k: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_double)), shape=(k,)).copy()
-    out = off, get(dl.cont, total * nc).reshape(total, nc), get(dl.xold, total), get(dl.h, total), n_seg, y_end, int(dl.passes)
+    out = off, get(dl.cont, total * nc).reshape(total, nc), get(dl.xold, total), get(dl.h, total), n_seg, y_end, int(dl.passes), int(dl.staging_bytes)
     L.ivp_dense_log_free(C.byref(dl))
     return out
+
+
+def _equals_the_device_form(got, d):
+    """offsets, cont, xold, h, n_seg and y_end of a C ABI call against solve_ivp_batch_dense's, bit for bit"""
+    off, cont, xold, h, ns, y_end = got
+    assert np.array_equal(off.astype(np.int64), d.seg_offsets.cpu().numpy()) and np.array_equal(ns, d.n_seg.cpu().numpy().astype(np.uint32))
+    assert np.array_equal(_bits(cont), _bits(d.seg_cont.cpu().numpy())) and np.array_equal(_bits(xold), _bits(d.seg_xold.cpu().numpy()))
+    assert np.array_equal(_bits(h), _bits(d.seg_h.cpu().numpy())) and np.array_equal(_bits(y_end), _bits(d.y_end.cpu().numpy()))
 
 
 @pytest.mark.parametrize("max_log", [0, 4096], ids=["filling-solve-on-the-device", "from-the-counting-block"])
 def test_host_entry_point_equals_the_device_form(max_log):
     f, y0, p, t0, t1 = _problem("cr3bp", 48)
     opts = ivp_amd.Options(method="DOPRI5", rtol=1e-6, atol=1e-9, max_log=max_log)
-    off, cont, xold, h, ns, y_end, passes = _host_form(f, y0, p, t0, t1, opts)
+    *got, passes, _ = _host_form(f, y0, p, t0, t1, opts)
     assert passes == (2 if max_log == 0 else 1)
     d = ivp_amd.solve_ivp_batch_dense(f, t0, t1, torch.as_tensor(y0, device=DEV), torch.as_tensor(p, device=DEV), opts)
-    assert np.array_equal(off.astype(np.int64), d.seg_offsets.cpu().numpy()) and np.array_equal(ns, d.n_seg.cpu().numpy().astype(np.uint32))
-    assert np.array_equal(_bits(cont), _bits(d.seg_cont.cpu().numpy())) and np.array_equal(_bits(xold), _bits(d.seg_xold.cpu().numpy()))
-    assert np.array_equal(_bits(h), _bits(d.seg_h.cpu().numpy())) and np.array_equal(_bits(y_end), _bits(d.y_end.cpu().numpy()))
+    _equals_the_device_form(got, d)
+
+
+def test_y_end_aliased_onto_y0_the_filling_solve_still_starts_from_y0():
+    """out.y_end == y0 with max_log = 0 (the counting solve writes the end state over y0, then a filling solve has to
+    run): host form and device form against the device form that does not alias"""
+    f, y0, p, t0, t1 = _problem("cr3bp", 48)
+    B = 48
+    opts = ivp_amd.Options(method="DOPRI5", rtol=1e-6, atol=1e-9, max_log=0)
+    d = ivp_amd.solve_ivp_batch_dense(f, t0, t1, torch.as_tensor(y0, device=DEV), torch.as_tensor(p, device=DEV), opts)
+    assert d.dense_info["passes"] == 2
+    *got, passes, _ = _host_form(f, y0, p, t0, t1, opts, alias=True)
+    assert passes == 2
+    _equals_the_device_form(got, d)
+    # the device entry point, out.y_end pointing at the y0 tensor; the log goes to buffers of exactly `total` records
+    total, nc = d.dense_info["segments"], int(d.seg_cont.shape[1])
+    L, ctx = _lib.load(), ivp_amd.default_context(0)
+    keep = []
+    copt = opts._c(f.n, keep)
+    prob = A._problem_c(f)
+    y0d, pd = torch.as_tensor(y0, device=DEV).clone(), torch.as_tensor(p, device=DEV)
+    t0d = torch.as_tensor(np.atleast_1d(np.asarray(t0, np.float64)), device=DEV)
+    t1d = torch.as_tensor(np.atleast_1d(np.asarray(t1, np.float64)), device=DEV)
+    off = torch.zeros(B + 1, dtype=torch.int64, device=DEV)
+    cont = torch.zeros((total, nc), dtype=torch.float64, device=DEV)
+    xold, h = torch.zeros(total, dtype=torch.float64, device=DEV), torch.zeros(total, dtype=torch.float64, device=DEV)
+    n_seg = torch.zeros(B, dtype=torch.int32, device=DEV)
+    dl = _lib.DenseLogT()
+    dl.offsets, dl.cont, dl.xold, dl.h, dl.capacity = off.data_ptr(), cont.data_ptr(), xold.data_ptr(), h.data_ptr(), total
+    r = _lib.BatchResultT()
+    r.y_end, r.n_seg = y0d.data_ptr(), n_seg.data_ptr()
+    stream = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    rc = L.ivp_batch_solve_dense_device(ctx.handle, C.byref(prob), B, y0d.data_ptr(), pd.data_ptr(), t0d.data_ptr(), len(t0d), t1d.data_ptr(), len(t1d),
+                                        C.byref(copt), C.byref(r), C.byref(dl), stream)
+    assert rc == 0, ctx.last_error()
+    assert dl.passes == 2 and dl.owned == 0 and int(dl.total) == total
+    _equals_the_device_form((off.cpu().numpy(), cont.cpu().numpy(), xold.cpu().numpy(), h.cpu().numpy(), n_seg.cpu().numpy().astype(np.uint32),
+                             y0d.cpu().numpy()), d)
+
+
+def test_host_entry_point_under_a_staging_cap_runs_trajectory_ranges(monkeypatch):
+    """IVP_DENSE_STAGING_BYTES below one whole-batch block: the host-pointer form's filling solve runs over more than one
+    range, same log"""
+    f, y0, p, t0, t1 = _problem("cr3bp", 48)
+    opts = ivp_amd.Options(method="DOPRI5", rtol=1e-6, atol=1e-9, max_log=0)
+    *whole, passes, staging = _host_form(f, y0, p, t0, t1, opts)
+    nc = whole[1].shape[1]
+    assert passes == 2 and staging == int(whole[4].max()) * (nc + 2) * 8 * 48    # one range: [max n_seg][ncoef n + 2] doubles x 48
+    cap = staging // 3                                                           # 16 trajectories' worth of the deepest block
+    monkeypatch.setenv("IVP_DENSE_STAGING_BYTES", str(cap))
+    *split, passes, sb = _host_form(f, y0, p, t0, t1, opts)
+    assert passes == 2 and 0 < sb <= cap
+    for a, b in zip(split, whole):
+        assert np.array_equal(_bits(a) if a.dtype == np.float64 else a, _bits(b) if b.dtype == np.float64 else b)
 
 
 def test_caller_buffers_too_small_report_the_total_then_fill():

@@ -495,7 +495,7 @@ def _host_form(f, y0, t1, opts, cap=None, alias=False):
         t, y = bufs[0][:total], bufs[1][:total]
     else:
         t = y = None
-    return rc, ctx.last_error(), off, t, y, hits, y_end, int(el.passes), total, bufs
+    return rc, ctx.last_error(), off, t, y, hits, y_end, int(el.passes), total, bufs, int(el.staging_bytes)
 
 
 @pytest.mark.parametrize("max_events,passes", [(64, 1), (2, 2), (0, 2)], ids=["one-pass-host-pack", "filling-solve", "count-only-then-fill"])
@@ -508,7 +508,7 @@ def test_host_entry_point_equals_the_device_form(max_events, passes):
     y_end_dev = dev[0].y_end.cpu().numpy()
 
     def same(h):
-        rc, err, off, t, y, hits, y_end, p, tot, _ = h
+        rc, err, off, t, y, hits, y_end, p, tot, _, _ = h
         assert rc == 0, err
         assert p == passes == dev[0].event_info["passes"] and tot == total
         assert np.array_equal(off.astype(np.int64), dev[1]) and np.array_equal(hits.astype(np.int64), dev[4])
@@ -518,7 +518,30 @@ def test_host_entry_point_equals_the_device_form(max_events, passes):
     same(_host_form(f, y0, t1, opts))                         # an owned host log
     same(_host_form(f, y0, t1, opts, cap=total))              # the caller's buffers, exactly large enough
     same(_host_form(f, y0, t1, opts, alias=True))             # y_end written over y0: the filling solve still starts from y0
-    rc, err, off, _, _, hits, _, _, tot, bufs = _host_form(f, y0, t1, opts, cap=total - 1)
+    rc, err, off, _, _, hits, _, _, tot, bufs, _ = _host_form(f, y0, t1, opts, cap=total - 1)
     assert rc == -105 and "hold" in err and tot == total
     assert np.array_equal(off.astype(np.int64), dev[1]) and np.array_equal(hits.astype(np.int64), dev[4])
     assert not bufs[0].any() and not bufs[1].any()            # never a truncated log
+
+
+def test_host_entry_point_under_a_staging_cap_runs_trajectory_ranges(monkeypatch):
+    """IVP_EVENT_STAGING_BYTES below one whole-batch block: the host-pointer form's filling solve runs over more than one
+    range, same log"""
+    B = 70
+    y0, t1 = _shapes_case(B)
+    f = ivp_amd.SHOZeroEvent(ivp_amd.EventConfig())
+    opts = ivp_amd.Options(max_events=0, **SHO_OPTS)
+    whole = _host_form(f, y0, t1, opts)
+    assert whole[0] == 0 and whole[7] == 2, whole[1]
+    one = int(whole[5].max()) * 3 * 8                         # one trajectory's block: [1 event][most hits][n + 1] doubles
+    assert whole[10] == one * B                               # one range
+    cap = one * B // 3                                        # 23 trajectories' worth of the deepest block: at least 4 ranges
+    monkeypatch.setenv("IVP_EVENT_STAGING_BYTES", str(cap))
+    split = _host_form(f, y0, t1, opts)
+    assert split[0] == 0 and split[7] == 2, split[1]
+    assert 0 < split[10] <= cap
+    assert split[8] == whole[8]
+    for i in (2, 5):                                          # offsets, hits
+        assert np.array_equal(split[i], whole[i])
+    for i in (3, 4, 6):                                       # t, y, y_end
+        assert np.array_equal(_bits(split[i]), _bits(whole[i]))
