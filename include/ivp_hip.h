@@ -356,18 +356,20 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  *
  * M y' = f(t, y) with a constant, possibly singular mass matrix and index-1/2/3 algebraic variables: ivp_radau_solve_dae*()
  * and ivp_radau_dae_check(), the three calls above plus `dae`.  The mass matrix comes from the problem -- a hiprtc snippet
- * compiled with IVP_RHS_HAS_MASS (below) -- and is evaluated once per trajectory, as the reference calls f.mass() once
+ * compiled with IVP_RHS_HAS_MASS (n <= 8) or IVP_RHS_HAS_MASS_COL (8 < n <= 64; both below) -- and is evaluated once per
+ * trajectory, as the reference calls f.mass() once
  * (radau.rs:358-359); a problem without the hook is solved with the identity, and gives what ivp_radau_solve*() gives.
  * ivp_radau_dae_t is the reference's nind1 / nind2 / nind3 (Option<usize> each: has_x = 0 means None), validated by its rules
  * in its order (radau.rs:210-246): none given -- nind1 = n (a pure ODE partition; dae == NULL means the same); nind1 omitted
  * -- inferred as n - nind2 - nind3, IVP_ERR_INVALID_DAE_PARTITION if nind2 + nind3 > n; else the three must sum to n.  A
  * negative count (not expressible in the reference) gets the same error.  Variables are ordered index-1 first, then
  * index-2, then index-3; the error scale of an index-2 (index-3) variable is divided by the step ratio hhfac (hhfac^2)
- * on every attempt (radau.rs:435-444).  nind2 + nind3 > 0 for a problem WITHOUT the mass hook is IVP_ERR_BAD_ARGUMENT
+ * on every attempt (radau.rs:435-444).  nind2 + nind3 > 0 for a problem WITHOUT a mass hook is IVP_ERR_BAD_ARGUMENT
  * ("not yet").  The refusals above (n > 64, events, FMA, variant = 3, banded storage and patterns beyond n = 8) apply
- * unchanged; a mass matrix and index-2 / index-3 variables stay n <= 8 (IVP_RHS_HAS_MASS), and a pure index-1 partition
- * of a larger problem takes the path of ivp_radau_solve*().
- * Deliberate deviation: a problem compiled with IVP_RHS_HAS_MASS is refused (IVP_ERR_BAD_ARGUMENT) by every other entry
+ * unchanged.  For 8 < n <= 64 a problem compiled with IVP_RHS_HAS_MASS_COL runs on the group kernels (one matrix row per
+ * lane; M is a fifth n^2 block of the trajectory's matrices and is copied into LDS by every launch) with every output form
+ * of the three calls; a pure index-1 partition of a larger problem without the hook takes the path of ivp_radau_solve*().
+ * Deliberate deviation: a problem compiled with IVP_RHS_HAS_MASS or IVP_RHS_HAS_MASS_COL is refused (IVP_ERR_BAD_ARGUMENT) by every other entry
  * point, ivp_radau_solve*() included -- the reference's explicit methods and BDF ignore IVP::mass silently, which solves a
  * different equation without saying so.
  */
@@ -721,9 +723,18 @@ int ivp_step_log_fetch_multi(ivp_shard_t *shards, int32_t n_shards, const ivp_pr
  * m starts zeroed (entries the hook never writes are 0, like the reference's full Matrix); p holds the trajectory's
  * parameters, so M may differ per trajectory.  Read by ivp_radau_solve_dae*() only; every other entry point refuses such a
  * problem (see there).
+ * flags & IVP_RHS_HAS_MASS_COL (ivp_rhs_compile_ex only, 8 < n <= 64, n_events == 0, alone or with IVP_RHS_HAS_JAC, not with
+ * IVP_RHS_HAS_MASS) -- the column form of the same hook for a component-form snippet (ode_comp, optional jac_col), the exact
+ * analogue of jac_col: write column `col` of M into column[0..n),
+ *     __device__ void mass_col(int col, double* column, const double* p);
+ * column[] is zeroed on entry (entries the hook never writes are 0); it is called once per column and trajectory.  Outside
+ * those bounds the call is IVP_ERR_BAD_ARGUMENT with a message that names the flag and the bound (n <= 8: use
+ * IVP_RHS_HAS_MASS).  A snippet whose mass_col does not compile is IVP_ERR_JIT.  The value is 16, not 8: 8 stays an
+ * unknown flag of ivp_rhs_compile_ex, and ivp_rhs_compile_sparse knows neither mass flag.
  */
 #define IVP_RHS_HAS_JAC 1u
 #define IVP_RHS_HAS_MASS 4u
+#define IVP_RHS_HAS_MASS_COL 16u
 int ivp_rhs_compile(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_t n_params, void **handle);
 int ivp_rhs_compile_events(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, void **handle);
 int ivp_rhs_compile_ex(ivp_ctx_t *ctx, const char *source, int32_t n, int32_t n_params, int32_t n_events, uint32_t flags, void **handle);

@@ -305,7 +305,7 @@ class DeviceIVP(IVP):
 
     def __init__(self, source: str, n: int, params: Sequence[float] = (), ctx: "Context" = None,
                  events: Sequence[EventConfig] = (), jac: bool = False, jac_sparsity=None, jac_storage: str = "full", *,
-                 mass: bool = False):
+                 mass_col: bool = False, mass: bool = False):
         """``events``: one EventConfig per event function; ``source`` must then also define
         ``__device__ void events(double x, const double* y, double* g, const double* p)``.
         ``jac=True``: ``source`` also overrides the trait's Jacobian (src/ivp.rs:67-107), used by BDF in place of the
@@ -326,7 +326,12 @@ class DeviceIVP(IVP):
         ``mass=True`` (n <= 8, not with ``jac_sparsity`` or ``jac_storage="banded"``): ``source`` also defines the trait's constant mass matrix
         (src/ivp.rs:111-120), ``__device__ void mass(double* m, const double* p)`` with ``m[row * n + col]``, zeroed on
         entry, evaluated once per trajectory with its parameters.  Such a problem is solved by ``ivp_amd.Radau`` only
-        (``M y' = f``, index-1/2/3 DAEs); every other solver refuses it instead of ignoring M."""
+        (``M y' = f``, index-1/2/3 DAEs); every other solver refuses it instead of ignoring M.
+        ``mass_col=True`` (8 < n <= 64, no ``events``, not with ``mass``, ``jac_sparsity`` or ``jac_storage="banded"``): the
+        same hook for a component-form ``source`` (``ode_comp``, optional ``jac_col``), by columns like ``jac_col``:
+        ``__device__ void mass_col(int col, double* column, const double* p)`` writes column ``col`` of M into
+        ``column[0..n)``, zeroed on entry.  ``ivp_amd.Radau`` then runs its group kernels (one matrix row per lane) on
+        ``M y' = f`` with index-1/2/3 sets of up to 64 variables; ``has_mass`` is true for either hook."""
         if jac_storage not in ("full", "banded"):
             raise ValueError(f'jac_storage must be "full" or "banded", got {jac_storage!r}')
         if jac_storage == "banded" and jac_sparsity is None:
@@ -339,7 +344,19 @@ class DeviceIVP(IVP):
             raise ValueError("mass=True needs n <= 8: the mass matrix is read by the Radau DAE call only")
         if mass and jac_sparsity is not None:
             raise ValueError("mass=True with jac_sparsity: a pattern is read by BDF on 8 < n <= 512, the mass matrix by Radau on n <= 8")
-        self.has_mass = bool(mass)
+        if mass_col and mass:
+            raise ValueError("mass_col=True with mass=True: one mass hook per problem (mass for n <= 8, mass_col for 8 < n <= 64)")
+        if mass_col and int(n) <= 8:
+            raise ValueError("mass_col=True needs 8 < n <= 64: for n <= 8 use mass=True")
+        if mass_col and int(n) > 64:
+            raise ValueError("mass_col=True needs 8 < n <= 64: the mass matrix is read by the Radau DAE call only")
+        if mass_col and len(events) > 0:
+            raise ValueError("mass_col=True with events: the Radau DAE call, the only reader of the mass matrix, has no event functions")
+        if mass_col and jac_storage == "banded":
+            raise ValueError('mass_col=True with jac_storage="banded": banded storage is BDF\'s, the mass matrix is Radau\'s')
+        if mass_col and jac_sparsity is not None:
+            raise ValueError("mass_col=True with jac_sparsity: a pattern is read by BDF, the mass matrix by Radau, which refuses patterns")
+        self.has_mass = bool(mass) or bool(mass_col)
         self.source = source
         self.n = int(n)
         self._params = tuple(float(v) for v in params)
@@ -353,13 +370,13 @@ class DeviceIVP(IVP):
         # process (a few hundred bytes of host state plus the loaded code objects).
         pattern = None if jac_sparsity is None else sparsity_csc(jac_sparsity, self.n)
         key = (source, self.n, self.n_params, len(self._events), bool(jac),
-               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()), jac_storage, bool(mass))
+               None if pattern is None else (pattern[0].tobytes(), pattern[1].tobytes()), jac_storage, bool(mass), bool(mass_col))
         h = _rhs_records.get(key)
         if h is None:
             h = C.c_void_p()
             if pattern is None:
                 rc = self._ctx.lib.ivp_rhs_compile_ex(self._ctx.handle, source.encode(), self.n, self.n_params,
-                                                      len(self._events), (1 if jac else 0) | (RHS_HAS_MASS if mass else 0), C.byref(h))
+                                                      len(self._events), (1 if jac else 0) | (RHS_HAS_MASS if mass else 0) | (RHS_HAS_MASS_COL if mass_col else 0), C.byref(h))
             else:
                 i32p = C.POINTER(C.c_int32)
                 rc = self._ctx.lib.ivp_rhs_compile_sparse(self._ctx.handle, source.encode(), self.n, self.n_params,
@@ -396,7 +413,8 @@ class DeviceIVP(IVP):
 
 RHS_BANDED = 2   # IVP_RHS_BANDED (include/ivp_hip.h)
 RHS_HAS_MASS = 4   # IVP_RHS_HAS_MASS
-_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern, jac_storage, mass) -> ivp_rhs_compile_ex / _sparse handle
+RHS_HAS_MASS_COL = 16   # IVP_RHS_HAS_MASS_COL (8 stays an unknown flag)
+_rhs_records: dict = {}   # (source, n, n_params, n_events, jac, sparsity pattern, jac_storage, mass, mass_col) -> ivp_rhs_compile_ex / _sparse handle
 
 
 def sparsity_csc(jac_sparsity, n: int):

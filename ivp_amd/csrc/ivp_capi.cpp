@@ -825,7 +825,9 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         a.ctl_facc2 = 1.0 / rad->scale_max;   // facr
         a.ctl_beta = rad->newton_tol;
         a.ctl_nstiff = (uint64_t)rad->newton_maxiter | (rad->has_newton_tol ? 0x100ull : 0ull) | (rad->predictive ? 0x200ull : 0ull);   // IVP_RAD_*
-        a.ctl_nstiff |= ((uint64_t)rad->nind2 << 12) | ((uint64_t)rad->nind3 << 16);   // IVP_RAD_NIND2_SHIFT / IVP_RAD_NIND3_SHIFT (both 0 unless the problem has a mass matrix)
+        // IVP_RAD_NIND2_SHIFT / IVP_RAD_NIND3_SHIFT and their _HI_ halves, radau_core.h (both counts 0 unless the problem has a mass matrix)
+        a.ctl_nstiff |= ((uint64_t)(rad->nind2 & 0xF) << 12) | ((uint64_t)(rad->nind3 & 0xF) << 16) |
+                        ((uint64_t)((rad->nind2 >> 4) & 0xF) << 20) | ((uint64_t)((rad->nind3 >> 4) & 0xF) << 24);
         a.has_ctl = 0;
     }
 
@@ -852,6 +854,7 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         // Radau's state lives behind the BDF members of the argument block (ivp_kargs.h), in buffers of its own
         // (n > 8, radau_group.h: the matrices are one contiguous column-major block [J, E1, E2r, E2i] per trajectory: same size)
         // ... a problem with a mass matrix keeps M behind the four matrices, and scal[n] and hhfac behind cont (radau_core.h)
+        // (either hook; the group form's layouts need the same sizes: [B][5 n n] blocks, slots 4 n + 2 .. 5 n + 2 of cont)
         const bool has_mass = prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit);
         HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (has_mass ? 5 : 4) * n * n * B));
         HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (has_mass ? 5 * n + 3 : 4 * n + 2) * B));
@@ -1709,7 +1712,18 @@ int ivp_rhs_compile_ex(ivp_ctx_t *ctx, const char *ode_source, int32_t n, int32_
     if (!ctx || !ode_source || !handle) return IVP_ERR_BAD_ARGUMENT;
     if (n < 1 || n > IVP_MAX_GROUP_N || n_params < 0 || n_params > IVP_MAX_P || n_events < 0 || n_events > 64)
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unsupported dimensions");
-    if (flags & ~(IVP_RHS_HAS_JAC | IVP_RHS_HAS_MASS)) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if (flags & ~(IVP_RHS_HAS_JAC | IVP_RHS_HAS_MASS | IVP_RHS_HAS_MASS_COL)) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "unknown flags 0x%x", flags);
+    if (flags & IVP_RHS_HAS_MASS_COL) {   // the column hook of the group Radau kernels (radau_group.h)
+        if (flags & IVP_RHS_HAS_MASS)
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS_COL with IVP_RHS_HAS_MASS: one mass hook per problem (mass for n <= %d, mass_col for %d < n <= %d)",
+                        IVP_MAX_N, IVP_MAX_N, IVP_RADAU_MAX_N);
+        if (n <= IVP_MAX_N)
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS_COL needs %d < n <= %d: for n <= %d use IVP_RHS_HAS_MASS", IVP_MAX_N, IVP_RADAU_MAX_N, IVP_MAX_N);
+        if (n > IVP_RADAU_MAX_N)
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS_COL needs %d < n <= %d: the mass matrix is read by the Radau DAE call only", IVP_MAX_N, IVP_RADAU_MAX_N);
+        if (n_events > 0)
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS_COL needs n_events == 0: the Radau DAE call, the only reader of the mass matrix, has no event functions");
+    }
     if ((flags & IVP_RHS_HAS_MASS) && n > IVP_MAX_N)
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "IVP_RHS_HAS_MASS needs n <= %d: the mass matrix is read by the Radau DAE call only", IVP_MAX_N);
     std::string log;

@@ -56,6 +56,7 @@ struct JitRhs {
     int device, n, np, ne;
     bool has_jac = false;   // the snippet defines jac(): IVP::jac override (src/ivp.rs:67-107)
     bool has_mass = false;  // the snippet defines mass(): IVP::mass (src/ivp.rs:111-120), read by the Radau DAE call only
+    bool has_mass_col = false;   // ... or mass_col(), its column form for the group Radau kernels (8 < n <= 64, radau_group.h)
     std::string ode_source;
     std::string sparsity_source;   // the pattern's tables as device code (empty: no pattern, or the snippet has its own jac_col)
     int n_groups = 0;
@@ -190,10 +191,13 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                           "#if IVP_USER_JAC\n"
                           "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
                           "#endif\n"
+                          "%s"
                           "}; }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n",
-                          r.n, r.np, flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
+                          r.n, r.np,
+                          r.has_mass_col ? "  static __device__ __forceinline__ void mass_col(int col, double* column, const double* p) { ::mass_col(col, column, p); }\n" : "",
+                          flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
             s += buf;
             return s;
         }
@@ -359,7 +363,7 @@ int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitMo
         }
     }
     if (!out) {   // compile-only check
-        if (r.has_mass) { r.checked_key = opt_key + "\n" + src; r.checked_code.swap(code); }
+        if (r.has_mass || r.has_mass_col) { r.checked_key = opt_key + "\n" + src; r.checked_code.swap(code); }
         return IVP_OK;
     }
     return load_module(r, code, out, coop_only);
@@ -368,7 +372,7 @@ int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitMo
 }  // namespace
 
 int ivp_jit_n_events(void *handle) { return handle ? ((JitRhs *)handle)->ne : 0; }
-bool ivp_jit_has_mass(void *handle) { return handle && ((JitRhs *)handle)->has_mass; }
+bool ivp_jit_has_mass(void *handle) { return handle && (((JitRhs *)handle)->has_mass || ((JitRhs *)handle)->has_mass_col); }
 
 int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log,
                     const int32_t *col_ptr, const int32_t *row_idx)
@@ -406,6 +410,7 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
     r->device = device;
     r->has_jac = (flags & IVP_RHS_HAS_JAC) != 0;
     r->has_mass = (flags & IVP_RHS_HAS_MASS) != 0;
+    r->has_mass_col = (flags & IVP_RHS_HAS_MASS_COL) != 0;
     r->n = n;
     r->np = n_params;
     r->ne = n_events;
@@ -420,9 +425,10 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
     }
     // compile the default configuration now so that syntax errors surface at ivp_rhs_compile() time -- for a problem with a
     // mass matrix that is the Radau module, the only one any entry point launches and the only one that instantiates mass()
-    const bool radau_only = r->has_mass && n_events == 0 && n <= IVP_MAX_N;
+    // ... or, with the column hook, the group Radau module (ivp_rhs_compile_ex has checked its bounds)
+    const bool radau_only = (r->has_mass && n_events == 0 && n <= IVP_MAX_N) || r->has_mass_col;
     int rc = compile_module(*r, radau_only ? IVP_RADAU : IVP_DOPRI5, IVP_FP_STRICT, n_events > 0, false, nullptr);
-    if (rc == IVP_OK && r->has_jac) rc = compile_module(*r, IVP_BDF, IVP_FP_STRICT, n_events > 0, false, nullptr);   // jac() is only instantiated by BDF
+    if (rc == IVP_OK && r->has_jac && !r->has_mass_col) rc = compile_module(*r, IVP_BDF, IVP_FP_STRICT, n_events > 0, false, nullptr);   // jac() is only instantiated by BDF
     if (rc != IVP_OK) {
         if (log) *log = r->log;
         delete r;

@@ -8,7 +8,7 @@
 int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int n_events, unsigned flags, void **handle, std::string *log,
                     const int32_t *col_ptr = nullptr, const int32_t *row_idx = nullptr);
 int ivp_jit_n_events(void *handle);
-bool ivp_jit_has_mass(void *handle);   // compiled with IVP_RHS_HAS_MASS: honoured by the Radau DAE call only
+bool ivp_jit_has_mass(void *handle);   // compiled with IVP_RHS_HAS_MASS or IVP_RHS_HAS_MASS_COL: honoured by the Radau DAE call only
 void ivp_jit_free(void *handle);
 // banded storage (IVP_RHS_BANDED): true and the bandwidths for a banded problem; lds_fits: the factors of a trajectory fit
 // the LDS budget of the banded kernels (bdf_band.h)

@@ -41,9 +41,13 @@ namespace IVP_NS {
 // ivp_kargs.h ctl_nstiff, as the Radau path fills it: newton_maxiter in the low byte, then two flags
 #define IVP_RAD_HAS_NEWTON_TOL 0x100ull
 #define IVP_RAD_PREDICTIVE 0x200ull
-// ... and, for problems with a mass matrix, the DAE partition: nind2 in bits 12..15, nind3 in bits 16..19 (nind1 = n - nind2 - nind3)
+// ... and, for problems with a mass matrix, the DAE partition (nind1 = n - nind2 - nind3), 8 bits each: the low four bits
+// of nind2 in bits 12..15 and of nind3 in bits 16..19 -- all there is for n <= 8 -- and the high four in bits 20..23 and
+// 24..27 (counts reach 64 in the group form, radau_group.h)
 #define IVP_RAD_NIND2_SHIFT 12
 #define IVP_RAD_NIND3_SHIFT 16
+#define IVP_RAD_NIND2_HI_SHIFT 20
+#define IVP_RAD_NIND3_HI_SHIFT 24
 
 // KC_SCOPE_KZ where ivp_pow takes the XOR partner (IVP_HOIST = 1, 2); elsewhere IVP_KZ_ARG is 0 and nothing would name it
 #if defined(__HIP_DEVICE_COMPILE__) && IVP_HOIST >= 1
@@ -61,6 +65,9 @@ IVP_HD uint32_t *radau_piv(const IvpKArgs &a) { return a.bdf_piv; }    // [2][B]
 // entry (k, local component c) of trajectory j in a [4][n] component-major array (cont, a dense-output segment)
 template <class MAP>
 IVP_HD size_t radau_cont_at(int k, int c, size_t B, uint32_t j) { return (size_t)(k * MAP::NT + MAP::gi(c)) * B + j; }
+// ... and of scal (HasMass), which sits behind cont, h_acc and err_acc; hhfac is slot 5 n + 2
+template <class MAP>
+IVP_HD size_t radau_scal_at(int c, size_t B, uint32_t j) { return (size_t)(4 * MAP::NT + 2 + MAP::gi(c)) * B + j; }
 
 // lu_decomp_complex (src/matrix/lu.rs:178-302), row-major; pivots packed 4 bits each.  Returns false if singular.
 template <int N>
@@ -252,6 +259,13 @@ template <class R, class = void>
 struct HasMass { enum { v = 0 }; };
 template <class R>
 struct HasMass<R, decltype((void)&R::mass)> { enum { v = 1 }; };
+// ... and its column form for the component-form problems of the group kernels (8 < n <= 64), the exact analogue of
+// jac_col:  static void mass_col(int col, double* column /* [n], zeroed on entry */, const double* p).  HasMass answers
+// to it too: radau_group.h specialises HasMass<GroupRhs<R, G>> on this trait.
+template <class R, class = void>
+struct HasMassCol { enum { v = 0 }; };
+template <class R>
+struct HasMassCol<R, decltype((void)&R::mass_col)> { enum { v = 1 }; };
 // entry e = row N + col of trajectory j's mass matrix: one coalesced load, used for all its products
 template <int N>
 IVP_HD double radau_mass_at(const IvpKArgs &a, uint32_t j, int e)
@@ -317,6 +331,23 @@ struct RadauOps {
     {
 #pragma unroll
         for (int c = 0; c < 4 * N * N; ++c) radau_mat(a)[(size_t)c * B + j] = 0.0;
+    }
+    // HasMass only: scal and hhfac, behind cont, h_acc and err_acc
+    static IVP_HD void init_scal(const IvpKArgs &a, size_t B, uint32_t j)
+    {
+#pragma unroll
+        for (int c = 4 * N + 2; c < 5 * N + 3; ++c) radau_cont(a)[(size_t)c * B + j] = 0.0;
+    }
+    // f.mass() is called once, on a zeroed full Matrix (radau.rs:283, :359): entries the hook never writes are 0
+    static IVP_HD void init_mass(const IvpKArgs &a, size_t, uint32_t j, const double *p)
+    {
+        double m[N][N];
+#pragma unroll
+        for (int r = 0; r < N; ++r)
+#pragma unroll
+            for (int c = 0; c < N; ++c) m[r][c] = 0.0;
+        R::mass(m, p);
+        radau_mat_store<N>(a, RAD_M, j, m);
     }
     static IVP_HD double tolst(const IvpKArgs &, const double (&rtol)[N]) { return rtol[0]; }   // newton_tol derives from it
     // before the attempts of one launch: the pivot state; returns the flag word
@@ -447,22 +478,10 @@ IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j)
     for (int c = 0; c < 4 * N; ++c) if (MAP::own(c % N)) radau_cont(a)[radau_cont_at<MAP>(c / N, c % N, B, j)] = 0.0;
     radau_cont(a)[(size_t)(4 * NT) * B + j] = 0.0;       // h_acc
     radau_cont(a)[(size_t)(4 * NT + 1) * B + j] = 0.0;   // err_acc
-    if constexpr (HasMass<R>::v) {
-#pragma unroll
-        for (int c = 4 * N + 2; c < 5 * N + 3; ++c) radau_cont(a)[(size_t)c * B + j] = 0.0;   // scal, hhfac
-    }
+    if constexpr (HasMass<R>::v) RadauOps<R>::init_scal(a, B, j);
     RadauOps<R>::init_mat(a, B, j);
-    if constexpr (HasMass<R>::v) {
-        // f.mass() is called once, on a zeroed full Matrix (radau.rs:283, :359): entries the hook never writes are 0.  Written
-        // before the early exits below, so the array is always defined.
-        double m[N][N];
-#pragma unroll
-        for (int r = 0; r < N; ++r)
-#pragma unroll
-            for (int c = 0; c < N; ++c) m[r][c] = 0.0;
-        R::mass(m, L.p);
-        radau_mat_store<N>(a, RAD_M, j, m);
-    }
+    // M is written once, before the early exits below, so the array is always defined
+    if constexpr (HasMass<R>::v) RadauOps<R>::init_mass(a, B, j, L.p);
 
     if (fabs(L.xend - L.x0) < 1e-15) {  // solve_ivp.rs:110-145
         if (FULL) {
@@ -509,7 +528,7 @@ IVP_HD int32_t radau_init_body(const IvpKArgs &a, uint32_t j)
     a.nfev[j] = 1;
     a.x[j] = L.x0; a.h[j] = h;
     radau_hold(a)[j] = h;
-    if constexpr (HasMass<R>::v) radau_cont(a)[(size_t)(5 * N + 2) * B + j] = h;   // hhfac = h, radau.rs:296
+    if constexpr (HasMass<R>::v) radau_cont(a)[(size_t)(5 * NT + 2) * B + j] = h;   // hhfac = h, radau.rs:296
     a.flags[j] = IVP_RAD_FIRST | IVP_RAD_CALLJAC | IVP_RAD_CALLDEC | (L.flags & IVP_F_FIRSTOUT);
     a.status[j] = IVP_RUNNING;
     return IVP_RUNNING;
@@ -570,10 +589,12 @@ IVP_HD bool radau_attempt(const IvpKArgs &a, uint32_t j, typename RadauLaneSel<R
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         if constexpr (HasMass<R>::v) {
-            // radau.rs:435-444: the persistent scal, divided on every pass that gets here
+            // radau.rs:435-444: the persistent scal, divided on every pass that gets here; the index sets are ranges of the
+            // component's index in the whole state (i itself in the thread form)
+            const int gi = OutMap<R>::type::gi(i);
             double sc = S.scal[i];
-            if (i >= S.nind1 && i < S.nind1 + S.nind2) sc = sc / S.hhfac;
-            if (i >= S.nind1 + S.nind2 && i < S.nind1 + S.nind2 + S.nind3) sc = sc / (S.hhfac * S.hhfac);   // powi(2)
+            if (gi >= S.nind1 && gi < S.nind1 + S.nind2) sc = sc / S.hhfac;
+            if (gi >= S.nind1 + S.nind2 && gi < S.nind1 + S.nind2 + S.nind3) sc = sc / (S.hhfac * S.hhfac);   // powi(2)
             S.scal[i] = sc;
             scal[i] = sc;
         } else scal[i] = S.atol[i] + S.rtol[i] * fabs(S.y[i]);
@@ -859,12 +880,17 @@ IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_
     if constexpr (HasMass<R>::v) {
         S.nind2 = (int)((a.ctl_nstiff >> IVP_RAD_NIND2_SHIFT) & 0xFull);
         S.nind3 = (int)((a.ctl_nstiff >> IVP_RAD_NIND3_SHIFT) & 0xFull);
-        S.nind1 = N - S.nind2 - S.nind3;
-        S.hhfac = radau_cont(a)[(size_t)(5 * N + 2) * B + j];
-        // before the first pass that counts a step nothing has divided scal yet: it is the initial one (radau.rs:361-364)
+        if constexpr (NT > 15) {   // counts past four bits exist only there
+            S.nind2 |= (int)((a.ctl_nstiff >> IVP_RAD_NIND2_HI_SHIFT) & 0xFull) << 4;
+            S.nind3 |= (int)((a.ctl_nstiff >> IVP_RAD_NIND3_HI_SHIFT) & 0xFull) << 4;
+        }
+        S.nind1 = NT - S.nind2 - S.nind3;
+        S.hhfac = radau_cont(a)[(size_t)(5 * NT + 2) * B + j];
+        // before the first pass that counts a step nothing has divided scal yet: it is the initial one (radau.rs:361-364);
+        // a lane without a component (group form) keeps that one: nothing reads it
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            S.scal[i] = S.nstep0 == 0 ? S.atol[i] + S.rtol[i] * fabs(S.y[i]) : radau_cont(a)[(size_t)(4 * N + 2 + i) * B + j];
+            S.scal[i] = (S.nstep0 == 0 || !MAP::own(i)) ? S.atol[i] + S.rtol[i] * fabs(S.y[i]) : radau_cont(a)[radau_scal_at<MAP>(i, B, j)];
     }
     L.flags = S.flags & IVP_F_FIRSTOUT;
     L.x0 = S.x0;
@@ -896,8 +922,8 @@ IVP_HD uint32_t radau_chunk_body(const IvpKArgs &a, uint32_t j, int32_t &status_
     radau_cont(a)[(size_t)(4 * NT + 1) * B + js] = S.err_acc;
     if constexpr (HasMass<R>::v) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) radau_cont(a)[(size_t)(4 * N + 2 + i) * B + js] = S.scal[i];
-        radau_cont(a)[(size_t)(5 * N + 2) * B + js] = S.hhfac;
+        for (int i = 0; i < N; ++i) if (MAP::own(i)) radau_cont(a)[radau_scal_at<MAP>(i, B, js)] = S.scal[i];
+        radau_cont(a)[(size_t)(5 * NT + 2) * B + js] = S.hhfac;
     }
     a.facold[js] = S.faccon;
     O.end(a, B, js);

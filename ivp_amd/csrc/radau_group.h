@@ -2,7 +2,7 @@
 // component and ONE matrix row, the three factors stay in LDS for the whole launch.  Device only.
 //
 // There is no attempt here: group_init_body / group_chunk_body (rk_group.h, M_RADAU) run radau_core.h's bodies on
-// GroupRhs<R, G> -- mass = Identity, pure ODEs, strict arithmetic only.  This file holds the group form of their policy,
+// GroupRhs<R, G> -- strict arithmetic only.  This file holds the group form of their policy,
 // RadauOps<GroupRhs<R, G>>, over BdfG::eval_jac / lu_decomp / lin_solve (bdf_group.h, unchanged: J and the real factor E1),
 // and RadauG: the group's LDS and the complex LU and solve of E2 = E2r + i E2i (lu.rs:178-302, linear.rs:140-217) over lanes.
 //
@@ -20,6 +20,14 @@
 // call_decomp is clear -- the only case in which an attempt uses factors it did not compute itself -- so `nlu` and every
 // result bit are independent of how attempts are cut into launches.
 // All barriers are workgroup barriers of a ONE-WAVEFRONT workgroup: groups of a wavefront may diverge around them.
+//
+// M y' = f.  A component-form functor with a `mass_col` member (HasMassCol, radau_core.h) makes HasMass<GroupRhs<R, G>> true,
+// and the bodies' mass sites and DAE index sets are compiled in.  M is a fifth n^2 block of the trajectory's global block
+// (J, E1, E2r, E2i, M: 5 n^2 doubles per trajectory, column-major), filled once by the init body, column c by lane c.  It is
+// constant and is read n times per Newton pass, so begin() copies it into the group's LDS on EVERY launch (unlike the
+// factors it is always valid) and the assembly and the mass-contribution sums read it from there: NGROUP n^2 doubles more
+// LDS, 32 KB at n = 64, paid by the mass instantiations only.  Everything here stays behind `if constexpr (MASS)`: a
+// functor without the hook compiles to what it compiled to.
 #pragma once
 
 namespace IVP_NS {
@@ -51,6 +59,12 @@ struct RadauG {
     {
         __shared__ double ivp_rad_f[NGROUP * 3 * NT];
         return ivp_rad_f + (size_t)grp() * 3 * NT;
+    }
+    // ... and, for a functor with mass_col only (nothing else names it), this group's copy of M, column-major
+    static __device__ __forceinline__ double *mass()
+    {
+        __shared__ double ivp_rad_mass[NGROUP * NN];
+        return ivp_rad_mass + (size_t)grp() * NN;
     }
 
     // lu_decomp_complex (src/matrix/lu.rs:178-302) in place on the column-major pair (ar, ai); pivots to piv[0..NT-2].
@@ -171,15 +185,18 @@ struct RadauG {
     }
 };
 
+// the bodies ask HasMass about the functor they run on, GroupRhs<R, G>: it has a mass matrix when R has the column hook
+template <class R, int G>
+struct HasMass<GroupRhs<R, G>, void> { enum { v = HasMassCol<R>::v }; };
+
 // The group form of the attempt's policy (radau_core.h): J and the write-through copies of the factors in the trajectory's
 // global block, the factors and pivots the solves read in the group's LDS, one row per lane.
 template <class R, int G>
 struct RadauOps<GroupRhs<R, G>> {
     using RG = RadauG<R, G>;
     using BG = BdfG<R, G>;
-    enum { NT = RG::NT, NN = RG::NN };
-    static_assert(!HasMass<R>::v, "RadauOps<GroupRhs>: the group form has no mass matrix (mass = Identity, pure ODEs)");
-    double *jac, *fac_mem, *fac;     // global: J, then E1, E2r, E2i; LDS: E1, E2r, E2i
+    enum { NT = RG::NT, NN = RG::NN, MASS = HasMassCol<R>::v, NMAT = MASS ? 5 : 4 };   // matrices in a trajectory's global block
+    double *jac, *fac_mem, *fac;     // global: J, then E1, E2r, E2i (then M); LDS: E1, E2r, E2i
     uint32_t *piv_mem, *piv;         // global and LDS: the pivot rows of E1, then of E2
     struct Factor {};                // the factors are resident: nothing to hand back
 
@@ -189,8 +206,25 @@ struct RadauOps<GroupRhs<R, G>> {
     }
     static __device__ __forceinline__ void init_mat(const IvpKArgs &a, size_t, uint32_t j)
     {
-        double *jac0 = radau_mat(a) + (size_t)j * 4 * NN;
+        double *jac0 = radau_mat(a) + (size_t)j * NMAT * NN;
         for (int e = RG::gl(); e < NN; e += G) jac0[e] = 0.0;
+    }
+    // MASS only: this lane's scal and the group's hhfac, behind cont, h_acc and err_acc (radau_scal_at, slot 5 n + 2)
+    static __device__ __forceinline__ void init_scal(const IvpKArgs &a, size_t B, uint32_t j)
+    {
+        using MAP = typename OutMap<GroupRhs<R, G>>::type;
+        if (MAP::own(0)) radau_cont(a)[radau_scal_at<MAP>(0, B, j)] = 0.0;
+        radau_cont(a)[(size_t)(5 * NT + 2) * B + j] = 0.0;
+    }
+    // f.mass() is called once, on a zeroed Matrix (radau.rs:283, :359): M is zeroed by the whole group, then
+    // lane c fills columns c, c + G, ... the way BdfG::eval_jac calls jac_col -- entries the hook does not write stay 0.0
+    static __device__ __forceinline__ void init_mass(const IvpKArgs &a, size_t, uint32_t j, const double *p)
+    {
+        double *m0 = radau_mat(a) + ((size_t)j * NMAT + 4) * NN;
+        for (int e = RG::gl(); e < NN; e += G) m0[e] = 0.0;
+        __syncthreads();   // the zeroes have landed before another lane's column does
+        for (int col = RG::gl(); col < NT; col += G) R::mass_col(col, m0 + (size_t)col * NT, p);
+        __syncthreads();
     }
     static __device__ __forceinline__ double tolst(const IvpKArgs &a, const double (&)[1])   // component 0's, in every lane
     {
@@ -199,7 +233,7 @@ struct RadauOps<GroupRhs<R, G>> {
     __device__ __forceinline__ uint32_t begin(const IvpKArgs &a, size_t, uint32_t j)
     {
         const uint32_t flags = a.flags[j];
-        jac = radau_mat(a) + (size_t)j * 4 * NN;
+        jac = radau_mat(a) + (size_t)j * NMAT * NN;
         fac_mem = jac + NN;
         piv_mem = radau_piv(a) + (size_t)j * 2 * NT;
         fac = RG::factors();
@@ -208,6 +242,12 @@ struct RadauOps<GroupRhs<R, G>> {
 #pragma unroll 8
             for (int e = RG::gl(); e < 3 * NN; e += G) fac[e] = fac_mem[e];
             for (int e = RG::gl(); e < 2 * NT; e += G) piv[e] = piv_mem[e];
+        }
+        if constexpr (MASS) {   // M is constant and always valid: every launch brings it in (coalesced)
+            double *ms = RG::mass();
+            const double *m0 = jac + 4 * NN;
+#pragma unroll 8
+            for (int e = RG::gl(); e < NN; e += G) ms[e] = m0[e];
         }
         __syncthreads();
         return flags;
@@ -219,7 +259,7 @@ struct RadauOps<GroupRhs<R, G>> {
 
     __device__ __forceinline__ void eval_jac(const IvpKArgs &, uint32_t, double x, const double (&y)[1], const double *p) const { BG::eval_jac(x, y, p, jac); }
     // E1, E2r and E2i are assembled together (one pass over J; lane <-> row: each column is one coalesced load), then E1 is
-    // factorised ...
+    // factorised ...  (MASS: e1 = m fac1 - j, e2r = m alphn - j, e2i = m betan with m = M[i][c] from LDS)
     __device__ __forceinline__ bool decomp_e1(const IvpKArgs &, uint32_t, double fac1, double alphn, double betan, uint32_t &nlu, Factor &) const
     {
         double *e1 = fac, *e2r = fac + NN, *e2i = fac + 2 * NN;
@@ -229,7 +269,9 @@ struct RadauOps<GroupRhs<R, G>> {
 #pragma unroll 8
             for (int c = 0; c < NT; ++c) {
                 const double jv = jac[c * NT + i];
-                const double id = i == c ? 1.0 : 0.0;
+                double id;
+                if constexpr (MASS) id = RG::mass()[c * NT + i];
+                else id = i == c ? 1.0 : 0.0;
                 e1[c * NT + i] = id * fac1 - jv;
                 e2r[c * NT + i] = id * alphn - jv;
                 e2i[c * NT + i] = id * betan;
@@ -255,7 +297,8 @@ struct RadauOps<GroupRhs<R, G>> {
     __device__ __forceinline__ void load_e1(const IvpKArgs &, uint32_t, Factor &) const {}
     __device__ __forceinline__ void solve_e1(const Factor &, double (&b)[1]) const { BG::lin_solve(fac, piv, b); }
     __device__ __forceinline__ void solve_e2(const IvpKArgs &, uint32_t, double (&br)[1], double (&bi)[1]) const { RG::lin_solve_complex(fac + NN, fac + 2 * NN, piv + NT, br[0], bi[0]); }
-    // mass contributions over ALL j, the identity's zeros multiplied out: f1, f2, f3 are published as three n-vectors
+    // mass contributions over ALL j, the identity's zeros multiplied out (MASS: row i of M, one conflict-free LDS read per
+    // j across the owning lanes): f1, f2, f3 are published as three n-vectors
     __device__ __forceinline__ void mass_row3(const IvpKArgs &, uint32_t, int, const double (&f1)[1], const double (&f2)[1], const double (&f3)[1],
                                               double &sum1, double &sum2, double &sum3) const
     {
@@ -267,7 +310,9 @@ struct RadauOps<GroupRhs<R, G>> {
         sum1 = 0.0; sum2 = 0.0; sum3 = 0.0;
 #pragma unroll 8
         for (int jj = 0; jj < NT; ++jj) {
-            const double mij = i == jj ? 1.0 : 0.0;
+            double mij;
+            if constexpr (MASS) mij = RG::mass()[jj * NT + RG::row()];
+            else mij = i == jj ? 1.0 : 0.0;
             sum1 -= mij * fv[jj];
             sum2 -= mij * fv[NT + jj];
             sum3 -= mij * fv[2 * NT + jj];
@@ -282,7 +327,10 @@ struct RadauOps<GroupRhs<R, G>> {
         __syncthreads();
         double sum = 0.0;
 #pragma unroll 8
-        for (int jj = 0; jj < NT; ++jj) sum += (i == jj ? 1.0 : 0.0) * fv[jj];
+        for (int jj = 0; jj < NT; ++jj) {
+            if constexpr (MASS) sum += RG::mass()[jj * NT + RG::row()] * fv[jj];
+            else sum += (i == jj ? 1.0 : 0.0) * fv[jj];
+        }
         return sum;
     }
 };

@@ -2,9 +2,9 @@
 
 Radau IIA(5), the L-stable 3-stage order-5 implicit Runge-Kutta method, on the device (strict arithmetic): pure ODEs with
 up to 64 states -- beyond 8 a ``DeviceIVP`` in component form (``ode_comp``, optional ``jac_col``; no ``jac_sparsity``, no
-banded storage) or ``Dense64()``, one matrix row per lane with the factors in LDS -- and, for up to 8 states,
-``M y' = f(t, y)`` with a constant, possibly singular mass matrix -- a ``DeviceIVP(..., mass=True)`` -- and index-1/2/3
-algebraic variables (``nind1`` / ``nind2`` / ``nind3``).
+banded storage) or ``Dense64()``, one matrix row per lane with the factors in LDS -- and ``M y' = f(t, y)`` with a
+constant, possibly singular mass matrix -- a ``DeviceIVP(..., mass=True)`` for up to 8 states, ``mass_col=True`` (the
+component form's column hook) from 9 to 64 -- and index-1/2/3 algebraic variables (``nind1`` / ``nind2`` / ``nind3``).
 ``solve_ivp(..., Options(method="RADAU"))`` still answers ``IVP_ERR_UNSUPPORTED_METHOD``; this class is the way in, and it
 carries the struct fields ``solve_ivp`` cannot reach.  Besides the blocking ``solve`` / ``solve_batch`` (bounded ``max_log``
 logs) it has the forms the other methods have for batches whose step counts are not known in advance:

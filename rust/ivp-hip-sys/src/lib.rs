@@ -41,6 +41,7 @@ pub const IVP_RHS_JIT: i32 = 1000;
 pub const IVP_RHS_HAS_JAC: u32 = 1;
 pub const IVP_RHS_BANDED: u32 = 2;
 pub const IVP_RHS_HAS_MASS: u32 = 4;
+pub const IVP_RHS_HAS_MASS_COL: u32 = 16; // mass_col(), 8 < n <= 64 (8 is not a flag)
 
 #[repr(C)]
 pub struct ivp_problem_t {

@@ -28,4 +28,6 @@ wait
 run radau_group_strict rk_radau_group.hip -DIVP_FAST=0 &
 # the group-per-trajectory Radau kernels (radau_group.h) at n = 9, 16, 32, 33, 64: tools/radau_group_resources.hip
 run radau_group "$TOOLS/radau_group_resources.hip" -DIVP_FAST=0 -I. &
+# ... and their mass-matrix instantiations (mass_col functor, hiprtc modules only): tools/radau_group_dae_resources.hip
+run radau_group_dae "$TOOLS/radau_group_dae_resources.hip" -DIVP_FAST=0 -I. &
 wait
