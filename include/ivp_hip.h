@@ -34,7 +34,7 @@ extern "C" {
 
 /* Method: same order as `enum Method`, src/solve/options.rs:14-27. The explicit RK methods (RK23, DOPRI5,
  * DOP853, the fixed-step RK4) and the variable-order implicit BDF are on the accelerated path of solve_ivp().  RADAU
- * runs on the device through its direct per-method call, ivp_radau_solve*() below (n <= 64); as ivp_options_t.method
+ * runs on the device through its direct per-method call, ivp_radau_solve*() below (n <= 64, hiprtc problems n <= 512); as ivp_options_t.method
  * it still returns IVP_ERR_UNSUPPORTED_METHOD from the solve_ivp() entry points. */
 typedef enum {
     IVP_RK23 = 0,
@@ -338,10 +338,14 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
 
 /*
  * Radau IIA(5), the direct per-method call: B independent RADAU::builder()...build().solve(f, x0, y0, xend, rtol, atol,
- * Some(&mut DefaultSolOut)) calls (src/methods/radau.rs:19-127) for pure ODEs with the identity mass matrix, n <= 64,
+ * Some(&mut DefaultSolOut)) calls (src/methods/radau.rs:19-127) for pure ODEs with the identity mass matrix, n <= 512,
  * strict arithmetic: one lane per trajectory for n <= 8; for 8 < n <= 64 (the built-in IVP_RHS_DENSE_64, and hiprtc problems
  * in component form, ode_comp with an optional jac_col) one group of 16 / 32 / 64 lanes per trajectory, one matrix row per
- * lane, the three factors of the attempt resident in LDS -- 3 n^2 doubles, which is what sets the bound.  ivp_radau_settings_t carries the struct fields solve_ivp() cannot reach; the fields it can come
+ * lane, the three factors of the attempt resident in LDS -- 3 n^2 doubles, which is what sets that bound; for 64 < n <= 512
+ * (hiprtc problems in component form without a mass hook only: no built-in beyond IVP_RHS_DENSE_64 is instantiated) one
+ * wavefront per trajectory, ceil(n / 64) matrix rows per lane, J and the three factors in global memory -- 4 n^2 doubles per
+ * trajectory, 8 MB at n = 512, 32 GB for B = 4096: an allocation that fails is IVP_ERR_HIP with HIP's out-of-memory text.
+ * ivp_radau_settings_t carries the struct fields solve_ivp() cannot reach; the fields it can come
  * from ivp_options_t: rtol / atol (scalar or vector), max_steps (0 = unlimited, the solve_ivp convention), t_eval with
  * or without t_eval_offsets, first_step, max_step, min_step, dense_output, max_log, chunk_attempts, profile.
  * opt->method is ignored.  Arguments otherwise as for ivp_batch_solve_device / ivp_batch_solve; settings == NULL means
@@ -349,7 +353,7 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  * [coef][component]; ivp_dense_eval_device(method = IVP_RADAU) evaluates them.
  * Errors, reported before the device is touched: the ConfigErrors of radau.rs:132-262 (MUST_BE_POSITIVE: newton_maxiter;
  * OUT_OF_RANGE: uround, safety_factor, newton_maxiter > 15; INVALID_SCALE_FACTORS; INVALID_STEP_SIZE: first_step == 0;
- * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 64, problems
+ * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 64 (a built-in problem, or one with a mass hook), problems
  * with event functions, fp_mode = FMA, variant = 3 and, for n > 8, a problem compiled with IVP_RHS_BANDED or with a
  * jac_sparsity pattern (ivp_rhs_compile_sparse).  The CSR one-pass / dense / events / multi-device forms are not on this
  * path yet.

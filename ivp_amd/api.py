@@ -299,7 +299,7 @@ class DeviceIVP(IVP):
     ``params`` are the values of the struct's fields (``p[...]`` inside ``ode``).
     For ``8 < n <= 512`` the snippet defines the component form
     ``__device__ double ode_comp(int i, double x, const double* y, const double* p)`` instead (one wavefront per
-    trajectory; RK23 / DOPRI5 / DOP853 / RK4 / BDF, and ``ivp_amd.Radau`` up to n = 64; ``events`` keeps the whole-state signature).
+    trajectory; RK23 / DOPRI5 / DOP853 / RK4 / BDF, and ``ivp_amd.Radau``; ``events`` keeps the whole-state signature).
     """
     rhs_id = 1000
 

@@ -687,7 +687,15 @@ int ivp_host::radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, 
     const int rc = validate(ctx, prob, B, opt, n_out, p_out, rad->dae_call ? IVP_VALIDATE_RADAU_DAE : IVP_VALIDATE_RADAU);
     if (rc != IVP_OK) return rc;
     const int n = *n_out;
-    if (n > IVP_RADAU_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_RADAU_MAX_N);
+    // 64 < n <= 512 is the wide form of radau_group.h: compiled problems without a mass hook.  rk_radau_group.hip instantiates no
+    // built-in beyond id 102, so the larger built-ins (100: n = 100, 101: n = 256) stay refused
+    const bool wide_ok = prob->rhs_id == IVP_RHS_JIT && !ivp_jit_has_mass(prob->jit) && n <= IVP_RADAU_WIDE_MAX_N;
+    if (n > IVP_RADAU_MAX_N && !wide_ok) {
+        if (prob->rhs_id != IVP_RHS_JIT)
+            return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d) for a built-in problem -- compile it (ode_comp) for n <= %d",
+                        n, IVP_RADAU_MAX_N, IVP_RADAU_WIDE_MAX_N);
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_RADAU_MAX_N);
+    }
     if (n > IVP_MAX_N && prob->rhs_id == IVP_RHS_JIT) {   // radau_group.h factorises full matrices from a full Jacobian
         if (ivp_jit_band(prob->jit, nullptr, nullptr, nullptr))
             return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for a problem compiled with IVP_RHS_BANDED (n = %d): not yet", n);
@@ -856,8 +864,9 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         // ... a problem with a mass matrix keeps M behind the four matrices, and scal[n] and hhfac behind cont (radau_core.h)
         // (either hook; the group form's layouts need the same sizes: [B][5 n n] blocks, slots 4 n + 2 .. 5 n + 2 of cont)
         const bool has_mass = prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit);
-        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (has_mass ? 5 : 4) * n * n * B));
-        HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (has_mass ? 5 * n + 3 : 4 * n + 2) * B));
+        // (byte counts in size_t: 4 n^2 doubles per trajectory is 8 MB at n = 512; a failed allocation is the HIP_TRY error)
+        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (size_t)(has_mass ? 5 : 4) * (size_t)n * (size_t)n * B));
+        HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (size_t)(has_mass ? 5 * n + 3 : 4 * n + 2) * B));
         HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B * (group ? (size_t)n : 1)));   // n > 8 (radau_group.h): [B][2][n] pivot rows
         a.bdf_jac = (double *)ctx->rad_mat.p;
         a.bdf_d = (double *)ctx->rad_cont.p;

@@ -182,7 +182,7 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
         s += join(k_src_rk_global_h);   // compact_append
         s += join(k_src_rk_group_h);
         s += join(k_src_bdf_group_h);
-        if (radau) {   // radau_group.h: 8 < n <= 64 (the host refuses everything else), G >= n lanes per trajectory
+        if (radau) {   // radau_group.h: 8 < n <= 64 with G >= n lanes per trajectory, 64 < n <= 512 with G = 64 and several rows per lane
             s += join(k_src_radau_core_h);
             s += join(k_src_radau_group_h);
             std::snprintf(buf, sizeof buf,

@@ -53,5 +53,9 @@ hipError_t ivp_launch_radau_strict(int what, int rhs_id, int full, const IvpKArg
 // group-per-trajectory Radau IIA(5) kernels (rk_radau_group.hip: radau_group.h, strict arithmetic, 8 < n <= 64: built-in
 // right-hand side 102); grid = `trajectories` one-wave blocks
 hipError_t ivp_launch_radau_group_strict(int what, int rhs_id, int full, const IvpKArgs &a, uint32_t trajectories, hipStream_t s);
-// largest n of the Radau path: the three factors of a trajectory (3 n^2 doubles) stay resident in LDS (radau_group.h)
+// largest n of the Radau path with the three factors of a trajectory (3 n^2 doubles) resident in LDS (radau_group.h): the
+// bound for the built-in problems and for a problem with a mass matrix (IVP_RHS_HAS_MASS_COL)
 #define IVP_RADAU_MAX_N 64
+// ... and of its wide form (several rows per lane, every matrix in global memory: 4 n^2 doubles per trajectory, 8 MB at
+// n = 512): compiled (hiprtc) problems in component form without a mass hook
+#define IVP_RADAU_WIDE_MAX_N 512

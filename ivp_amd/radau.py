@@ -1,8 +1,10 @@
 """``ivp_amd.Radau`` -- the direct per-method call ``RADAU::builder()...build().solve(..)`` (src/methods/radau.rs:19-127).
 
 Radau IIA(5), the L-stable 3-stage order-5 implicit Runge-Kutta method, on the device (strict arithmetic): pure ODEs with
-up to 64 states -- beyond 8 a ``DeviceIVP`` in component form (``ode_comp``, optional ``jac_col``; no ``jac_sparsity``, no
-banded storage) or ``Dense64()``, one matrix row per lane with the factors in LDS -- and ``M y' = f(t, y)`` with a
+up to 512 states -- beyond 8 a ``DeviceIVP`` in component form (``ode_comp``, optional ``jac_col``; no ``jac_sparsity``, no
+banded storage) or ``Dense64()``: up to 64 states one matrix row per lane with the factors in LDS, from 65 to 512 (compiled
+problems only) several rows per lane with J and the three factors in global memory, 4 n^2 doubles per trajectory (8 MB at
+n = 512: an allocation that fails is ``HipError``) -- and ``M y' = f(t, y)`` with a
 constant, possibly singular mass matrix -- a ``DeviceIVP(..., mass=True)`` for up to 8 states, ``mass_col=True`` (the
 component form's column hook) from 9 to 64 -- and index-1/2/3 algebraic variables (``nind1`` / ``nind2`` / ``nind3``).
 ``solve_ivp(..., Options(method="RADAU"))`` still answers ``IVP_ERR_UNSUPPORTED_METHOD``; this class is the way in, and it

@@ -31,3 +31,7 @@ run radau_group "$TOOLS/radau_group_resources.hip" -DIVP_FAST=0 -I. &
 # ... and their mass-matrix instantiations (mass_col functor, hiprtc modules only): tools/radau_group_dae_resources.hip
 run radau_group_dae "$TOOLS/radau_group_dae_resources.hip" -DIVP_FAST=0 -I. &
 wait
+# the wide form of the group Radau kernels (64 < n <= 512, hiprtc modules only) at n = 65, 128, 129, 257, 512:
+# tools/radau_wide_resources.hip
+run radau_wide "$TOOLS/radau_wide_resources.hip" -DIVP_FAST=0 -I. &
+wait
