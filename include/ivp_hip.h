@@ -354,9 +354,9 @@ int ivp_batch_wait(ivp_ctx_t *ctx);
  * Errors, reported before the device is touched: the ConfigErrors of radau.rs:132-262 (MUST_BE_POSITIVE: newton_maxiter;
  * OUT_OF_RANGE: uround, safety_factor, newton_maxiter > 15; INVALID_SCALE_FACTORS; INVALID_STEP_SIZE: first_step == 0;
  * NEGATIVE_TOLERANCE / TOLERANCE_SIZE_MISMATCH) and IVP_ERR_BAD_ARGUMENT with a "not yet" message for n > 64 (a built-in problem, or one with a mass hook), problems
- * with event functions, fp_mode = FMA, variant = 3 and, for n > 8, a problem compiled with IVP_RHS_BANDED or with a
- * jac_sparsity pattern (ivp_rhs_compile_sparse).  The CSR one-pass / dense / events / multi-device forms are not on this
- * path yet.
+ * with event functions (their one way in is ivp_radau_solve_events*, declared behind ivp_event_log_t below), fp_mode = FMA,
+ * variant = 3 and, for n > 8, a problem compiled with IVP_RHS_BANDED or with a jac_sparsity pattern
+ * (ivp_rhs_compile_sparse).  The multi-device forms are not on this path yet.
  *
  * M y' = f(t, y) with a constant, possibly singular mass matrix and index-1/2/3 algebraic variables: ivp_radau_solve_dae*()
  * and ivp_radau_dae_check(), the three calls above plus `dae`.  The mass matrix comes from the problem -- a hiprtc snippet
@@ -634,6 +634,30 @@ int ivp_batch_solve_events_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, siz
 int ivp_batch_solve_events(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                            const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
                            ivp_batch_result_t *out, ivp_event_log_t *ev);
+/*
+ * ... through the direct Radau call: the way in for Radau IIA(5) with event functions.  The contract above, member for
+ * member (event-major runs, who owns t / y, IVP_ERR_LOG_CAPACITY, passes, staging_bytes, IVP_EVENT_STAGING_BYTES,
+ * out->t_events / y_events NULL); `out` receives what the counting solve computes -- end state, counters, njev / nlu, t_eval
+ * samples with the terminal event's appended sample (eval_idx = -1, t_term), the bounded step log with the terminal point
+ * appended, dense segments, n_event_hits.  opt->method is ignored.  settings / dae follow ivp_radau_submit_device
+ * (dae == NULL: the ODE rules, a problem with a mass matrix is refused); both are read before the first solve is
+ * submitted and kept for the filling solves.  Radau refines every root inline, in the stepping kernels.
+ * This is the ONLY Radau entry point that accepts a problem with event functions: ivp_radau_check, ivp_radau_dae_check and
+ * every other ivp_radau_* call keep refusing one.  Refused here (IVP_ERR_BAD_ARGUMENT, before the device is touched), on
+ * top of everything ivp_radau_solve_dae_device refuses: a problem without event functions, and n > 64 ("Radau with event
+ * functions for n = %d: not yet (n <= 64)").  For 8 < n <= 64 the problem is a compiled component-form one without a mass
+ * hook (IVP_RHS_HAS_MASS_COL cannot be compiled with event functions).  ivp_radau_events_check runs those checks alone.
+ */
+int ivp_radau_events_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                           const ivp_radau_dae_t *dae, char *message, size_t message_len);
+int ivp_radau_solve_events_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                                  ivp_event_log_t *ev, void *hip_stream);
+int ivp_radau_solve_events(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                           ivp_event_log_t *ev);
 /* an owned device log (owned = 1, device >= 0) into the caller's device buffers of ev->total records, on hip_stream;
  * the owned memory is released and ev then points at the caller's buffers (owned = 0) */
 int ivp_event_log_fetch_device(ivp_event_log_t *ev, double *t, double *y, void *hip_stream);

@@ -119,6 +119,7 @@ EXPORTS = (
     "ivp_radau_settings_default", "ivp_radau_solve", "ivp_radau_solve_device", "ivp_options_check", "ivp_radau_check",
     "ivp_radau_dae_check", "ivp_radau_solve_dae", "ivp_radau_solve_dae_device",
     "ivp_radau_submit_device", "ivp_radau_solve_logged_device", "ivp_radau_solve_dense_device",
+    "ivp_radau_events_check", "ivp_radau_solve_events_device", "ivp_radau_solve_events",
 )
 
 ERRORS = {
@@ -244,6 +245,13 @@ def load():
     L.ivp_batch_solve_events_device.argtypes = solve_args + [C.POINTER(EventLogT), C.c_void_p]
     L.ivp_batch_solve_events.restype = C.c_int
     L.ivp_batch_solve_events.argtypes = solve_args + [C.POINTER(EventLogT)]
+    # ... through the direct Radau call, the only Radau entry point that accepts event functions
+    L.ivp_radau_events_check.restype = C.c_int
+    L.ivp_radau_events_check.argtypes = L.ivp_radau_dae_check.argtypes
+    L.ivp_radau_solve_events_device.restype = C.c_int
+    L.ivp_radau_solve_events_device.argtypes = radau_args + [C.POINTER(EventLogT), C.c_void_p]
+    L.ivp_radau_solve_events.restype = C.c_int
+    L.ivp_radau_solve_events.argtypes = radau_args + [C.POINTER(EventLogT)]
     L.ivp_event_log_fetch_device.restype = C.c_int
     L.ivp_event_log_fetch_device.argtypes = [C.POINTER(EventLogT), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ivp_event_log_free.restype = None

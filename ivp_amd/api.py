@@ -990,8 +990,6 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
     copt = options._c(n, keep)
     method = options.method_enum
     if _radau is not None:   # the direct Radau call (ivp_amd.Radau): Options.method is ignored
-        if _events is not None:
-            raise ValueError("Radau: the CSR event form is not on its path (Radau has no events yet)")
         method = Method.RADAU
     per_traj = options.t_eval_per_trajectory is not None
     if per_traj:
@@ -1133,8 +1131,12 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         if not on_device:
             raise ValueError("the CSR event log takes device arrays")
         stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
-        rc = ctx.lib.ivp_batch_solve_events_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
-                                                   ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_events), stream)
+        if _radau is not None:   # Radau.solve_batch_events: the one Radau call that takes a problem with event functions
+            rc = ctx.lib.ivp_radau_solve_events_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len, ptr(t1a), t1_len,
+                                                       C.byref(copt), C.byref(_radau), dae_ref, C.byref(r), C.byref(_events), stream)
+        else:
+            rc = ctx.lib.ivp_batch_solve_events_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                       ptr(t1a), t1_len, C.byref(copt), C.byref(r), C.byref(_events), stream)
     elif _steplog is not None:   # solve_ivp_batch_logged: ONE integration that also records every accepted step (page pool + gather)
         import torch
         if not on_device:
@@ -1396,7 +1398,8 @@ def solve_ivp_batch_dense(f: IVP, t0, t1, y0, params=None, options: Options = No
     return res
 
 
-def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None) -> BatchSolution:
+def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
+                           _radau=None, _radau_dae=None) -> BatchSolution:
     """B independent ``solve_ivp`` calls with EVERY occurrence of every event (``Solution.t_events`` / ``y_events``,
     src/solve/solution.rs:10-11), not capped at ``max_events``: the occurrences come back as a CSR log on the device.
 
@@ -1411,10 +1414,12 @@ def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = N
     of [n_events][max hits][n + 1] doubles per trajectory are packed into the CSR arrays (``passes`` = 2).
     ``max_events=0`` counts first and always fills.  The library-owned log is copied once into the returned tensors (the
     total is not known before the solve), so the result is briefly held twice.  The log cannot overflow, so no overflow warning is ever issued;
-    ``IVP_EVENT_STAGING_BYTES`` caps the staging block at the price of one filling solve per trajectory range."""
+    ``IVP_EVENT_STAGING_BYTES`` caps the staging block at the price of one filling solve per trajectory range.
+    ``_radau`` / ``_radau_dae`` (``ivp_amd.Radau.solve_batch_events``): every solve is the direct Radau call
+    (``ivp_radau_solve_events_device``), whose refusals come from the library."""
     import torch
     options = options or Options()
-    if not f.n_events():
+    if not f.n_events() and _radau is None:
         raise ValueError("solve_ivp_batch_events: the problem defines no event functions")
     ctx = ctx or default_context(y0.device.index or 0 if _is_torch(y0) else 0)
     dev = y0.device if _is_torch(y0) else torch.device("cuda", ctx.device)
@@ -1424,10 +1429,10 @@ def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = N
     t0d, t1d = tt(t0), tt(t1)
     n, B = int(y0d.shape[0]), int(y0d.shape[1])
     el = _lib.EventLogT()
-    offsets = torch.zeros(f.n_events() * B + 1, dtype=torch.int64, device=dev)
+    offsets = torch.zeros(max(f.n_events(), 1) * B + 1, dtype=torch.int64, device=dev)
     el.offsets = offsets.data_ptr()
     try:
-        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, options, ctx, _events=el)
+        res = solve_ivp_batch(f, t0d, t1d, y0d, pd, options, ctx, _events=el, _radau=_radau, _radau_dae=_radau_dae)
         total = int(el.total)
         t = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
         y = torch.empty((max(total, 1), n), dtype=torch.float64, device=dev)

@@ -703,7 +703,11 @@ int ivp_host::radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, 
             return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for a problem with a jac_sparsity pattern (n = %d): not yet", n);
     }
     const int n_events = prob->rhs_id == IVP_RHS_JIT ? ivp_jit_n_events(prob->jit) : n > IVP_MAX_N ? 0 : kRhsEvents[prob->rhs_id];
-    if (n_events > 0) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for problems with event functions: not yet on the accelerated path");
+    if (rad->events_call) {   // ivp_radau_solve_events*(): the thread form (n <= 8) and the LDS group form (n <= 64) locate events
+        if (n_events == 0) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "the problem defines no event functions: there is no event log to deliver");
+        if (n > IVP_RADAU_MAX_N) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with event functions for n = %d: not yet (n <= %d)", n, IVP_RADAU_MAX_N);
+    } else if (n_events > 0)
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for problems with event functions: not yet on the accelerated path");
     if (opt->fp_mode != IVP_FP_STRICT) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with fp_mode = FMA: not yet (strict arithmetic only)");
     if (opt->variant == 3) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau with variant = 3 (lane-cooperative kernels): not yet");
     if (rad->uround <= 1e-35 || rad->uround >= 1.0) return fail(ctx, IVP_ERR_OUT_OF_RANGE, "uround = %g outside (1e-35, 1)", rad->uround);
@@ -955,7 +959,7 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         // kernel refines them, one lane per noted step.  Explicit methods, thread-per-trajectory / lane-cooperative kernels.
         bool any_terminal = false;
         for (int i = 0; i < n_events; ++i) any_terminal = any_terminal || (a.ev_terminal_dev ? opt->ev_terminal_vec[i] : opt->ev_terminal[i < 4 ? i : 3]) != 0;
-        if (!any_terminal && !group && opt->method != IVP_BDF && tune().defer_events != 0) {
+        if (!any_terminal && !group && opt->method != IVP_BDF && opt->method != IVP_RADAU && tune().defer_events != 0) {   // (the implicit methods search inline)
             const uint64_t ncoef = opt->method == IVP_DOPRI5 ? 5 : (opt->method == IVP_DOP853 ? 8 : 4);
             const uint64_t fields = 4 + 3 * (uint64_t)n_events + (uint64_t)n + ncoef * (uint64_t)n;
             const uint64_t cap = std::max<uint64_t>((uint64_t)n_events * a.max_events, 1);   // every noted step fills at least one output slot
@@ -1685,6 +1689,17 @@ int ivp_batch_solve_multi_host(ivp_ctx_t *const *ctxs, int32_t n_ctx, const ivp_
 {
     return multi_host_impl(ctxs, n_ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, nullptr);
 }
+
+}  // extern "C"
+
+int ivp_host::solve_host(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
+                         const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, RadauCall *rad)
+{
+    ivp_ctx_t *one[1] = {ctx};
+    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, rad);
+}
+
+extern "C" {
 
 int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
                     const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,

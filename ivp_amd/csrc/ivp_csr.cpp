@@ -253,7 +253,7 @@ int csr_solve_host(ivp_ctx *ctx, const CsrKind &k, const CsrInputs &in, ivp_batc
     if (depth > 0) k.bind(r, block.data(), depth, B);
     r.*k.counts = counts.data();
     *k.staging_bytes = block.size() * sizeof(double);
-    int rc = ivp_batch_solve(ctx, in.prob, B, in.y0, in.params, in.t0, in.t0_len, in.t1, in.t1_len, &k.count_opt, &r);
+    int rc = solve_host(ctx, in.prob, B, in.y0, in.params, in.t0, in.t0_len, in.t1, in.t1_len, &k.count_opt, &r, k.rad);
     if (rc != IVP_OK) return rc;
     const ivp_run_stats_t stats = ctx->stats;
     if (out->*k.counts) std::memcpy(out->*k.counts, counts.data(), sizeof(uint32_t) * runs);

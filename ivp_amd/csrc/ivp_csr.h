@@ -58,7 +58,8 @@ struct CsrKind {
 
 // what a host-pointer entry point asks of its arrays (the device forms leave that to the solve)
 int check_host_inputs(ivp_ctx *ctx, const CsrInputs &in);
-// steps 1 - 4 on device pointers (ctx's device is current) and on host pointers (the counting solve is ivp_batch_solve)
+// steps 1 - 4 on device pointers (ctx's device is current) and on host pointers (the counting solve is ivp_batch_solve, or --
+// k.rad -- the host form of the direct Radau call: ivp_host::solve_host)
 int csr_solve_device(ivp_ctx *ctx, const CsrKind &k, const CsrInputs &in, ivp_batch_result_t *out, hipStream_t s);
 int csr_solve_host(ivp_ctx *ctx, const CsrKind &k, const CsrInputs &in, ivp_batch_result_t *out);
 

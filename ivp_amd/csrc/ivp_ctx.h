@@ -166,6 +166,7 @@ struct RadauCall : ivp_radau_settings_t {
     int dae_call = 0;                    // ivp_radau_solve_dae*(): a problem with a mass matrix is accepted
     const ivp_radau_dae_t *dae = nullptr;
     int nind2 = 0, nind3 = 0;            // set by radau_validate
+    int events_call = 0;                 // ivp_radau_solve_events*(): the one call that accepts (and requires) event functions
     RadauCall(const ivp_radau_settings_t *s, int dae_call_, const ivp_radau_dae_t *dae_) : dae_call(dae_call_), dae(dae_)
     {
         if (s) *static_cast<ivp_radau_settings_t *>(this) = *s;
@@ -180,6 +181,9 @@ int radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_
 // step-log driver (ivp_log.cpp) and the staging driver of the dense and event logs (ivp_csr.cpp) run, as often as they need it
 int solve_device(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
                  const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, void *hip_stream, RadauCall *rad);
+// ... and its host-pointer form on one context: ivp_batch_solve, or -- rad != NULL -- ivp_radau_solve / ivp_radau_solve_dae
+int solve_host(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params, const double *t0, size_t t0_len,
+               const double *t1, size_t t1_len, const ivp_options_t *opt, ivp_batch_result_t *out, RadauCall *rad);
 // restores the caller's current HIP device when a multi-device entry point returns
 struct DeviceGuard {
     int dev = -1;

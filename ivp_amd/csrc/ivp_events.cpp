@@ -10,6 +10,8 @@
 // up to n_events * max_events steps of 4 + 3 n_events + n + ncoef n doubles per trajectory when a quarter of the free memory
 // holds them (inline refinement otherwise).  This file holds what is the event log's own: the argument checks, the
 // description of the kind, the host packing loop, the entry points and the log's ownership calls with their width table.
+// ivp_radau_solve_events*() are the same log over the direct Radau call (CsrKind::rad): the one Radau entry point that accepts a
+// problem with event functions (radau_validate's events mode, ivp_capi.cpp); Radau refines every root inline.
 #include "ivp_csr.h"
 
 #include <cstdint>
@@ -33,15 +35,16 @@ namespace {
 std::mutex g_owned_mu;
 std::unordered_map<const void *, size_t> g_owned_n;
 
-// arguments of both entry points; *nev_out = the problem's number of event functions
+// arguments of all entry points; *nev_out = the problem's number of event functions.  rad != NULL: the direct Radau call
+// (ivp_radau_solve_events*), whose *opt has been made Radau's (method, has_settings) by the caller
 int check_args(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_batch_result_t *out, const ivp_event_log_t *ev,
-               int *n_out, int *np_out, size_t *nev_out)
+               int *n_out, int *np_out, size_t *nev_out, RadauCall *rad = nullptr)
 {
     if (!opt || !out || !ev || !ev->offsets) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null options / out / ev / ev->offsets");
     if (out->t_events || out->y_events)
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "out.t_events / y_events are the bounded layout: leave them NULL, the occurrences go to `ev`");
     if ((ev->t != nullptr) != (ev->y != nullptr)) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "ivp_event_log_t: t and y must both be given or both be NULL");
-    int rc = validate(ctx, prob, B, opt, n_out, np_out);
+    int rc = rad ? radau_validate(ctx, prob, B, opt, rad, n_out, np_out) : validate(ctx, prob, B, opt, n_out, np_out);
     if (rc != IVP_OK) return rc;
     const size_t nev = result_shape(prob, opt, *n_out).nev;
     if (nev == 0) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "the problem defines no event functions: there is no event log to deliver");
@@ -110,6 +113,22 @@ CsrKind event_kind(ivp_ctx *ctx, const ivp_options_t *opt, ivp_event_log_t *ev, 
     return k;
 }
 
+// opt as the Radau path reads it (submit_impl does the same): method and the explicit methods' controller fields are ignored
+ivp_options_t radau_options(const ivp_options_t *opt)
+{
+    ivp_options_t o = *opt;
+    o.method = IVP_RADAU;
+    o.has_settings = 0;
+    return o;
+}
+
+RadauCall radau_events_call(const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae)
+{
+    RadauCall call = radau_call(settings, dae);
+    call.events_call = 1;
+    return call;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,6 +163,71 @@ int ivp_batch_solve_events(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
     if (rc != IVP_OK) return rc;
     DeviceGuard restore_device;
     return csr_solve_host(ctx, event_kind(ctx, opt, ev, (size_t)n, nev, B), in, out);
+}
+
+// ---- the direct Radau call with event functions: the same log over the Radau solve (every round of the driver runs it with
+// the settings / partition copied here; the caller's structs are not read once the first submit has returned) ----
+
+int ivp_radau_events_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                           const ivp_radau_dae_t *dae, char *message, size_t message_len)
+{
+    ivp_ctx scratch;   // carries the message, owns no device memory, touches no HIP call
+    int n = 0, np = 0, rc;
+    if (!prob || !opt) rc = fail(&scratch, IVP_ERR_BAD_ARGUMENT, "null problem/options");
+    else {
+        const ivp_options_t o = radau_options(opt);
+        RadauCall call = radau_events_call(settings, dae);
+        rc = radau_validate(&scratch, prob, B, &o, &call, &n, &np);
+        if (rc == IVP_OK) {
+            const int nev = (int)result_shape(prob, &o, n).nev;
+            if (nev > 4 && !(o.ev_direction_vec && o.ev_terminal_vec && o.n_event_cfg == nev))
+                rc = fail(&scratch, IVP_ERR_BAD_ARGUMENT, "%d event functions need ev_direction_vec / ev_terminal_vec with n_event_cfg = %d entries", nev, nev);
+        }
+    }
+    if (message && message_len) std::snprintf(message, message_len, "%s", scratch.err.c_str());
+    return rc;
+}
+
+int ivp_radau_solve_events_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
+                                  ivp_event_log_t *ev, void *hip_stream)
+{
+    if (!ctx) return IVP_ERR_BAD_ARGUMENT;
+    ctx->err.clear();
+    if (!opt) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null options / out / ev / ev->offsets");
+    const ivp_options_t o = radau_options(opt);
+    RadauCall call = radau_events_call(settings, dae);
+    int n = 0, np = 0;
+    size_t nev = 0;
+    int rc = check_args(ctx, prob, B, &o, out, ev, &n, &np, &nev, &call);
+    if (rc != IVP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CsrKind k = event_kind(ctx, &o, ev, (size_t)n, nev, B);
+    k.rad = &call;
+    return csr_solve_device(ctx, k, CsrInputs{prob, B, y0, params, t0, t0_len, t1, t1_len, n, np}, out, (hipStream_t)hip_stream);
+}
+
+int ivp_radau_solve_events(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out, ivp_event_log_t *ev)
+{
+    if (!ctx) return IVP_ERR_BAD_ARGUMENT;
+    ctx->err.clear();
+    if (!opt) return fail(ctx, IVP_ERR_BAD_ARGUMENT, "null options / out / ev / ev->offsets");
+    const ivp_options_t o = radau_options(opt);
+    RadauCall call = radau_events_call(settings, dae);
+    int n = 0, np = 0;
+    size_t nev = 0;
+    int rc = check_args(ctx, prob, B, &o, out, ev, &n, &np, &nev, &call);
+    if (rc != IVP_OK) return rc;
+    const CsrInputs in{prob, B, y0, params, t0, t0_len, t1, t1_len, n, np};
+    rc = check_host_inputs(ctx, in);
+    if (rc != IVP_OK) return rc;
+    DeviceGuard restore_device;
+    CsrKind k = event_kind(ctx, &o, ev, (size_t)n, nev, B);
+    k.rad = &call;
+    return csr_solve_host(ctx, k, in, out);
 }
 
 int ivp_event_log_fetch_device(ivp_event_log_t *ev, double *t, double *y, void *hip_stream)

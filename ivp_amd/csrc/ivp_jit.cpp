@@ -191,11 +191,16 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                           "#if IVP_USER_JAC\n"
                           "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
                           "#endif\n"
-                          "%s"
+                          "%s%s"
                           "}; }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n",
                           r.n, r.np,
+                          // Event functions (ivp_radau_solve_events*; only modules of such problems get the line).  GroupRhs::events
+                          // has barriers inside so_events' root search, which the 64 / G groups of a wavefront enter and leave
+                          // independently: safe because these kernels' workgroup is ONE wavefront (__launch_bounds__(IVP_WAVE), one
+                          // block of IVP_WAVE lanes per launch -- bdf_group.h:31-32 states the rule).  Never a multi-wave workgroup here.
+                          r.ne > 0 ? "  static __device__ __forceinline__ void events(double x, const double* y, double* g, const double* p) { ::events(x, y, g, p); }\n" : "",
                           r.has_mass_col ? "  static __device__ __forceinline__ void mass_col(int col, double* column, const double* p) { ::mass_col(col, column, p); }\n" : "",
                           flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
             s += buf;
@@ -263,7 +268,7 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                   method, full, method, full,
                   (ctl && (method == IVP_RK23 || method == IVP_DOPRI5 || method == IVP_DOP853)) ? "true" : "false");
     s += buf;
-    if (r.ne > 0 && flavour == 1 && method != IVP_BDF) {
+    if (r.ne > 0 && flavour == 1 && method != IVP_BDF && method != IVP_RADAU) {   // deferred refinement: the explicit methods only
         std::snprintf(buf, sizeof buf,
                       "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_events(const IvpKArgs a)\n"
                       "{ ivp_jit::event_kernel_body<%d, ivp_jit::RhsUser>(a); }\n", method);
@@ -426,7 +431,8 @@ int ivp_jit_compile(int device, const char *ode_source, int n, int n_params, int
     // compile the default configuration now so that syntax errors surface at ivp_rhs_compile() time -- for a problem with a
     // mass matrix that is the Radau module, the only one any entry point launches and the only one that instantiates mass()
     // ... or, with the column hook, the group Radau module (ivp_rhs_compile_ex has checked its bounds)
-    const bool radau_only = (r->has_mass && n_events == 0 && n <= IVP_MAX_N) || r->has_mass_col;
+    // (a mass matrix with event functions: ivp_radau_solve_events* is the one call that runs it, with this module)
+    const bool radau_only = (r->has_mass && n <= IVP_MAX_N) || r->has_mass_col;
     int rc = compile_module(*r, radau_only ? IVP_RADAU : IVP_DOPRI5, IVP_FP_STRICT, n_events > 0, false, nullptr);
     if (rc == IVP_OK && r->has_jac && !r->has_mass_col) rc = compile_module(*r, IVP_BDF, IVP_FP_STRICT, n_events > 0, false, nullptr);   // jac() is only instantiated by BDF
     if (rc != IVP_OK) {

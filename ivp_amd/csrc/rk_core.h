@@ -1470,7 +1470,7 @@ IVP_HD bool so_events(const IvpKArgs &a, uint32_t j, Lane<R::N, R::P> &L, double
         for (int i = 0; i < NE; ++i) a.prev_event[(size_t)i * B + j] = g_curr[i];
         return false;
     }
-    if constexpr (M != M_BDF) {
+    if constexpr (M != M_BDF && M != M_RADAU) {   // the implicit methods refine inline: the host never gives them evd_rec
         if (a.evd_rec != nullptr) {
             so_events_note<M, R>(a, j, xold, x, y, cont, h, ixold, g_curr);
 #pragma unroll

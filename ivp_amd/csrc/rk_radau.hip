@@ -25,7 +25,6 @@ using namespace IVP_NS;
 template <class R, int FULL>
 hipError_t launch_one(int what, const IvpKArgs &a, uint32_t lanes, hipStream_t s)
 {
-    static_assert(R::NE == 0, "problems with event functions are not on the Radau path");
     const uint32_t per_wave = (what == IVP_LAUNCH_CHUNK && a.lpw) ? a.lpw : (uint32_t)IVP_WAVE;   // thin waves (ivp_kargs.h)
     const dim3 grid((lanes + per_wave - 1) / per_wave), block(IVP_WAVE);
     if (grid.x == 0) return hipSuccess;
@@ -57,7 +56,13 @@ hipError_t ivp_launch_radau_strict(int what, int rhs_id, int full, const IvpKArg
     case 8: return launch_rhs<IVP_NS::RhsLinear>(what, full, a, lanes, s);
     case 9: return launch_rhs<IVP_NS::RhsRobertson>(what, full, a, lanes, s);
     case 10: return launch_rhs<IVP_NS::RhsVdpEps>(what, full, a, lanes, s);
+    // problems with event functions (ivp_radau_solve_events*, the only call the host lets them through) always run FULL:
+    // DefaultSolOut with so_events, every root refined inline
+    case 11: return launch_one<IVP_NS::RhsShoEv, true>(what, a, lanes, s);
+    case 12: return launch_one<IVP_NS::RhsBall, true>(what, a, lanes, s);
+    case 13: return launch_one<IVP_NS::RhsCannon, true>(what, a, lanes, s);
+    case 14: return launch_one<IVP_NS::RhsRationalEv, true>(what, a, lanes, s);
     case 15: return launch_rhs<IVP_NS::RhsRobertsonJac>(what, full, a, lanes, s);   // analytic jac
     }
-    return hipErrorInvalidValue;   // problems with event functions (11..14): rejected by the host before any launch
+    return hipErrorInvalidValue;
 }

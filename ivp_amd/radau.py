@@ -12,7 +12,10 @@ carries the struct fields ``solve_ivp`` cannot reach.  Besides the blocking ``so
 logs) it has the forms the other methods have for batches whose step counts are not known in advance:
 ``solve_batch(..., wait=False)`` (a ``PendingBatch``; ``BatchPipeline.map(..., radau=...)`` overlaps several),
 ``solve_batch_logged`` (every accepted step, CSR, one integration) and ``solve_batch_dense`` (every segment, CSR, evaluated on
-the device).  Not there: events in any form, the multi-GPU entry points.
+the device).  Event functions have ONE way in, ``solve_batch_events``: every occurrence of every event as a CSR log, with
+everything a plain solve returns beside it (thread form up to 8 states, mass matrix included; component form without a mass
+hook up to 64).  Not there: events through the other Radau calls (``solve``, ``solve_batch``, ``solve_batch_logged``,
+``solve_batch_dense`` still refuse a problem with event functions), events beyond n = 64, the multi-GPU entry points.
 """
 from typing import Optional, Sequence
 
@@ -87,3 +90,14 @@ class Radau:
         ``solve_ivp_batch_dense`` with 4 n coefficients per segment; ``result.dense`` is a ``BatchContinuousOutput`` with
         ``Method.RADAU`` that evaluates y(t) on the device."""
         return api.solve_ivp_batch_dense(f, t0, t1, y0, params, options, ctx, _radau=self._c(), _radau_dae=self._dae(f))
+
+    def solve_batch_events(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None,
+                           ctx: api.Context = None) -> api.BatchSolution:
+        """Radau with event functions: every occurrence of every event of every trajectory as a CSR log
+        (``ivp_radau_solve_events_device``), no ``max_events`` to guess.  The result of ``solve_ivp_batch_events`` --
+        ``event_offsets``, ``t_events_csr``, ``y_events_csr``, ``events_of`` / ``events_all``, ``event_info`` with passes and
+        staging -- beside everything ``solve_batch`` returns (end state, counters, ``t_eval`` samples with a terminal event's
+        appended sample, the bounded step log, dense segments, ``n_event_hits``).  Host (numpy) arrays are moved to the device.
+        Refused by the library (``ConfigError``): a problem without event functions, more than 64 states, and everything
+        ``solve_batch`` refuses."""
+        return api.solve_ivp_batch_events(f, t0, t1, y0, params, options, ctx, _radau=self._c(), _radau_dae=self._dae(f))

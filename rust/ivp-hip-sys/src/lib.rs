@@ -331,6 +331,17 @@ extern "C" {
     pub fn ivp_batch_solve_events(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
                                   t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
                                   out: *mut ivp_batch_result_t, ev: *mut ivp_event_log_t) -> c_int;
+    // ... through the direct Radau call: the only Radau entry point that accepts event functions (n <= 64); dae may be null
+    pub fn ivp_radau_events_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,
+                                  dae: *const ivp_radau_dae_t, message: *mut c_char, message_len: usize) -> c_int;
+    pub fn ivp_radau_solve_events_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                         t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                         settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                         ev: *mut ivp_event_log_t, hip_stream: *mut c_void) -> c_int;
+    pub fn ivp_radau_solve_events(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                  t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                  settings: *const ivp_radau_settings_t, dae: *const ivp_radau_dae_t, out: *mut ivp_batch_result_t,
+                                  ev: *mut ivp_event_log_t) -> c_int;
     pub fn ivp_event_log_fetch_device(ev: *mut ivp_event_log_t, t: *mut f64, y: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn ivp_event_log_free(ev: *mut ivp_event_log_t);
     // one batch over several devices: N contexts driven by this thread, shards gathered by peer copies (xGMI)

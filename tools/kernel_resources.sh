@@ -34,4 +34,8 @@ wait
 # the wide form of the group Radau kernels (64 < n <= 512, hiprtc modules only) at n = 65, 128, 129, 257, 512:
 # tools/radau_wide_resources.hip
 run radau_wide "$TOOLS/radau_wide_resources.hip" -DIVP_FAST=0 -I. &
+# the Radau kernels of problems with event functions (the built-ins are in radau_strict above): the thread form at n = 8 and
+# n = 5 with a mass matrix, the group form at n = 16 and 64: tools/radau_events_resources.hip
+run radau_events "$TOOLS/radau_events_resources.hip" -DIVP_FAST=0 -I. &
+run radau_events_group "$TOOLS/radau_events_resources.hip" -DIVP_FAST=0 -DIVP_RES_GROUP -I. &
 wait
