@@ -436,6 +436,38 @@ int ivp_radau_submit_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B,
                             const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
                             const ivp_radau_settings_t *settings, const ivp_radau_dae_t *dae, ivp_batch_result_t *out,
                             void *hip_stream);
+/*
+ * Radau IIA(5) in BAND STORAGE: the direct call for a hiprtc problem compiled with IVP_RHS_BANDED (ivp_rhs_compile_sparse,
+ * 8 < n <= 512, pure ODE, no event functions) -- and for nothing else: any other problem is IVP_ERR_BAD_ARGUMENT with a
+ * message saying that this call has nothing to do for it.  Every entry point above keeps refusing such a problem ("not
+ * yet"); this is its one way in.  Arguments, settings == NULL, results and every other refusal (event functions, fp_mode =
+ * FMA, variant = 3, the ConfigErrors) are those of ivp_radau_check / ivp_radau_solve / ivp_radau_solve_device; there is no
+ * DAE partition.  variant 0, 1 and 2 behave alike.  `out` carries what a plain Radau solve returns: end state, h_next,
+ * status, the six counters, t_eval samples, the bounded step log, dense segments.
+ * Layout (ml = max(row - col), mu = max(col - row) of the declared pattern, ivp_rhs_jac_layout; KD = ml + mu): one
+ * contiguous block per trajectory in global memory holds J in LAPACK general-band form, WJ = ml + mu + 1 doubles per column
+ * (entry (i, j) at j WJ + mu + i - j), then E1 = fac1 I - J, E2r = alphn I - J and E2i = betan I in the factor form, W =
+ * 2 ml + mu + 1 doubles per column (entry (i, j) at j W + KD + i - j; the ml extra superdiagonals take the fill of row
+ * exchanges): (WJ + 3 W) n doubles per trajectory instead of 4 n^2 -- 15 n for a tridiagonal system, 60 KB instead of
+ * 8 MB at n = 512.  The Jacobian is formed by grouped forward differences (n_groups + 1 right-hand sides), E1 is factorised
+ * by the band LU of the BDF path, E2 by its complex counterpart.  Nothing is kept in LDS across attempts, so the results do
+ * not depend on chunk_attempts.
+ * Contract: for a finite right-hand side and a pattern that contains every structurally non-zero entry, every result --
+ * status, t_end, y_end, h_next, all six counters (Radau does not count Jacobian differences in nfev), t_eval samples, step
+ * log and dense segments -- equals bit for bit what ivp_radau_solve*() gives for the same source compiled WITHOUT a pattern
+ * (forward differences, full matrices).  Outside the claim, as for banded BDF: the sign of a zero and non-finite values.  A
+ * pattern that omits non-zero entries is an error of the caller that is not detected.
+ * Not here yet: the resumable, logged and CSR dense forms, event functions, mass matrices and DAE index sets, the
+ * multi-device forms, n <= 8, an analytic jac_col.
+ */
+int ivp_radau_banded_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                           char *message, size_t message_len);
+int ivp_radau_solve_banded(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, ivp_batch_result_t *out);
+int ivp_radau_solve_banded_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, ivp_batch_result_t *out, void *hip_stream);
 
 /*
  * Solution.t / Solution.y of B solve_ivp() calls in ONE call and ONE integration (ABI v5).

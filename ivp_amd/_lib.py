@@ -120,6 +120,7 @@ EXPORTS = (
     "ivp_radau_dae_check", "ivp_radau_solve_dae", "ivp_radau_solve_dae_device",
     "ivp_radau_submit_device", "ivp_radau_solve_logged_device", "ivp_radau_solve_dense_device",
     "ivp_radau_events_check", "ivp_radau_solve_events_device", "ivp_radau_solve_events",
+    "ivp_radau_banded_check", "ivp_radau_solve_banded_device", "ivp_radau_solve_banded",
 )
 
 ERRORS = {
@@ -198,6 +199,13 @@ def load():
     L.ivp_radau_solve.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1]]
     L.ivp_radau_solve_device.restype = C.c_int
     L.ivp_radau_solve_device.argtypes = solve_args[:-1] + [C.POINTER(RadauSettingsT), solve_args[-1], C.c_void_p]
+    # ... in band storage, for problems compiled with IVP_RHS_BANDED: the signatures of ivp_radau_check / ivp_radau_solve*
+    L.ivp_radau_banded_check.restype = C.c_int
+    L.ivp_radau_banded_check.argtypes = L.ivp_radau_check.argtypes
+    L.ivp_radau_solve_banded.restype = C.c_int
+    L.ivp_radau_solve_banded.argtypes = L.ivp_radau_solve.argtypes
+    L.ivp_radau_solve_banded_device.restype = C.c_int
+    L.ivp_radau_solve_banded_device.argtypes = L.ivp_radau_solve_device.argtypes
     L.ivp_radau_dae_check.restype = C.c_int
     L.ivp_radau_dae_check.argtypes = [C.POINTER(ProblemT), C.c_size_t, C.POINTER(OptionsT), C.POINTER(RadauSettingsT), C.POINTER(RadauDaeT),
                                       C.c_char_p, C.c_size_t]

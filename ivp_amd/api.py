@@ -926,7 +926,8 @@ class PendingBatch:
 
 
 def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ctx: Context = None,
-                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None, _radau=None, _radau_dae=None):
+                    out: BatchSolution = None, wait: bool = True, _steplog=None, _dense=None, _events=None, _radau=None, _radau_dae=None,
+                    _radau_band: bool = False):
     """B independent ``solve_ivp(f, t0[b], t1[b], y0[:, b], options)`` calls on the GPU.
 
     ``y0``: ``[n, B]`` float64, numpy (host path: staged through the library) or a CUDA torch tensor
@@ -1101,6 +1102,22 @@ def solve_ivp_batch(f: IVP, t0, t1, y0, params=None, options: Options = None, ct
         setattr(r, name, ptr(getattr(res, name)))
     prob = _problem_c(f)
     dae_ref = None if _radau_dae is None else C.byref(_radau_dae)   # NULL: the rules of ivp_radau_solve_device
+    if _radau_band:   # ivp_amd.Radau.solve_batch_banded: band storage, blocking, no partition -- the library refuses the rest
+        if _radau is None or _radau_dae is not None or not wait or _dense is not None or _events is not None or _steplog is not None:
+            raise ValueError("the banded Radau call is the blocking solve of a pure ODE")
+        if on_device:
+            import torch
+            stream = C.c_void_p(torch.cuda.current_stream(y0.device).cuda_stream)
+            rc = ctx.lib.ivp_radau_solve_banded_device(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                       ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(r), stream)
+        else:
+            rc = ctx.lib.ivp_radau_solve_banded(ctx.handle, C.byref(prob), B, ptr(y0), ptr(params), ptr(t0a), t0_len,
+                                                ptr(t1a), t1_len, C.byref(copt), C.byref(_radau), C.byref(r))
+        if rc != 0:
+            raise ConfigError(rc, ctx.last_error())
+        if options.profile:
+            res.stats = ctx.stats()
+        return res
     if not wait:
         if not on_device:
             raise ValueError("wait=False needs device arrays (the host-pointer entry point copies results back at the end)")
@@ -1449,7 +1466,7 @@ def solve_ivp_batch_events(f: IVP, t0, t1, y0, params=None, options: Options = N
 
 
 def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Options = None,
-              ctx: Context = None, _radau=None, _radau_dae=None) -> Solution:
+              ctx: Context = None, _radau=None, _radau_dae=None, _radau_band: bool = False) -> Solution:
     """``solve_ivp(&f, x0, xend, &y0, options) -> Result<Solution, Error>`` (solve_ivp.rs:99-108) for
     one trajectory, executed by the GPU kernels (a batch of one).  ``Err(..)`` becomes an exception."""
     options = options or Options()
@@ -1484,7 +1501,7 @@ def solve_ivp(f: IVP, x0: float, xend: float, y0: Sequence[float], options: Opti
         pr = np.asarray(f.params(), dtype=np.float64).reshape(f.n_params, 1) if f.n_params else None
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx, _radau=_radau, _radau_dae=_radau_dae)
+            r = solve_ivp_batch(f, x0, xend, y0.reshape(n, 1), pr, o, ctx, _radau=_radau, _radau_dae=_radau_dae, _radau_band=_radau_band)
         used = 0
         if r.n_log is not None:
             used = max(used, int(r.n_log[0]))

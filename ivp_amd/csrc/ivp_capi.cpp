@@ -696,7 +696,7 @@ int ivp_host::radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, 
                         n, IVP_RADAU_MAX_N, IVP_RADAU_WIDE_MAX_N);
         return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for n = %d: not yet on the accelerated path (n <= %d)", n, IVP_RADAU_MAX_N);
     }
-    if (n > IVP_MAX_N && prob->rhs_id == IVP_RHS_JIT) {   // radau_group.h factorises full matrices from a full Jacobian
+    if (!rad->band_call && n > IVP_MAX_N && prob->rhs_id == IVP_RHS_JIT) {   // radau_group.h factorises full matrices from a full Jacobian
         if (ivp_jit_band(prob->jit, nullptr, nullptr, nullptr))
             return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau for a problem compiled with IVP_RHS_BANDED (n = %d): not yet", n);
         if (ivp_jit_has_sparsity(prob->jit))
@@ -724,6 +724,10 @@ int ivp_host::radau_validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, 
             return fail(ctx, IVP_ERR_BAD_ARGUMENT, "Radau index-2 / index-3 variables for a problem without a mass matrix (IVP_RHS_HAS_MASS): not yet");
     }
     if (opt->has_first_step && opt->first_step == 0.0) return fail(ctx, IVP_ERR_INVALID_STEP_SIZE, "Radau: first_step is zero");
+    // ivp_radau_solve_banded*(): band storage (radau_band.h) is all this call has.  After every refusal the plain call shares
+    // with it, so that those keep their codes and texts.  (Such a problem is compiled, 8 < n <= 512, without a mass hook.)
+    if (rad->band_call && (prob->rhs_id != IVP_RHS_JIT || !ivp_jit_band(prob->jit, nullptr, nullptr, nullptr)))
+        return fail(ctx, IVP_ERR_BAD_ARGUMENT, "the banded Radau call needs a problem compiled with IVP_RHS_BANDED (ivp_rhs_compile_sparse): it has nothing to do for this one");
     return IVP_OK;
 }
 
@@ -840,6 +844,7 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         // IVP_RAD_NIND2_SHIFT / IVP_RAD_NIND3_SHIFT and their _HI_ halves, radau_core.h (both counts 0 unless the problem has a mass matrix)
         a.ctl_nstiff |= ((uint64_t)(rad->nind2 & 0xF) << 12) | ((uint64_t)(rad->nind3 & 0xF) << 16) |
                         ((uint64_t)((rad->nind2 >> 4) & 0xF) << 20) | ((uint64_t)((rad->nind3 >> 4) & 0xF) << 24);
+        if (rad->band_call) a.ctl_nstiff |= IVP_RAD_BAND_CALL;   // read by ivp_jit_launch alone: the band-storage module
         a.has_ctl = 0;
     }
 
@@ -869,7 +874,14 @@ int submit_impl(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const doubl
         // (either hook; the group form's layouts need the same sizes: [B][5 n n] blocks, slots 4 n + 2 .. 5 n + 2 of cont)
         const bool has_mass = prob->rhs_id == IVP_RHS_JIT && ivp_jit_has_mass(prob->jit);
         // (byte counts in size_t: 4 n^2 doubles per trajectory is 8 MB at n = 512; a failed allocation is the HIP_TRY error)
-        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (size_t)(has_mass ? 5 : 4) * (size_t)n * (size_t)n * B));
+        // ... the banded call (radau_band.h): J by bands, then E1, E2r, E2i in the factor layout: (WJ + 3 W) n doubles per trajectory
+        uint64_t mat_doubles = (uint64_t)(has_mass ? 5 : 4) * (uint64_t)n * (uint64_t)n;
+        if (rad && rad->band_call) {
+            uint64_t jac_doubles = 0, lu_doubles = 0;
+            (void)ivp_rhs_jac_layout(prob->jit, nullptr, nullptr, nullptr, &jac_doubles, &lu_doubles);
+            mat_doubles = jac_doubles + 3 * lu_doubles;
+        }
+        HIP_TRY(ctx, ctx->rad_mat.reserve(sizeof(double) * (size_t)mat_doubles * B));
         HIP_TRY(ctx, ctx->rad_cont.reserve(sizeof(double) * (size_t)(has_mass ? 5 * n + 3 : 4 * n + 2) * B));
         HIP_TRY(ctx, ctx->rad_piv.reserve(sizeof(uint32_t) * 2 * B * (group ? (size_t)n : 1)));   // n > 8 (radau_group.h): [B][2][n] pivot rows
         a.bdf_jac = (double *)ctx->rad_mat.p;
@@ -1227,6 +1239,40 @@ int ivp_radau_solve_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, 
     ivp_radau_settings_t dflt;
     ivp_radau_settings_default(&dflt);
     RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, &call);
+    if (rc != IVP_OK) return rc;
+    return ivp_batch_wait(ctx);
+}
+
+// Radau in band storage (radau_band.h): the direct call for problems compiled with IVP_RHS_BANDED, and only for them
+int ivp_radau_banded_check(const ivp_problem_t *prob, size_t B, const ivp_options_t *opt, const ivp_radau_settings_t *settings,
+                           char *message, size_t message_len)
+{
+    ivp_ctx scratch;
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    int n = 0, np = 0, rc;
+    if (!prob || !opt) rc = fail(&scratch, IVP_ERR_BAD_ARGUMENT, "null problem/options");
+    else {
+        ivp_options_t o = *opt;
+        o.method = IVP_RADAU;
+        o.has_settings = 0;
+        RadauCall call(settings ? settings : &dflt, 0, nullptr);
+        call.band_call = 1;
+        rc = radau_validate(&scratch, prob, B, &o, &call, &n, &np);
+    }
+    copy_message(scratch, message, message_len);
+    return rc;
+}
+
+int ivp_radau_solve_banded_device(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                                  const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                                  const ivp_radau_settings_t *settings, ivp_batch_result_t *out, void *hip_stream)
+{
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    call.band_call = 1;
     const int rc = submit_impl(ctx, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, hip_stream, &call);
     if (rc != IVP_OK) return rc;
     return ivp_batch_wait(ctx);
@@ -1709,6 +1755,18 @@ int ivp_radau_solve(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const d
     ivp_radau_settings_default(&dflt);
     ivp_ctx_t *one[1] = {ctx};
     RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, &call);
+}
+
+int ivp_radau_solve_banded(ivp_ctx_t *ctx, const ivp_problem_t *prob, size_t B, const double *y0, const double *params,
+                           const double *t0, size_t t0_len, const double *t1, size_t t1_len, const ivp_options_t *opt,
+                           const ivp_radau_settings_t *settings, ivp_batch_result_t *out)
+{
+    ivp_radau_settings_t dflt;
+    ivp_radau_settings_default(&dflt);
+    ivp_ctx_t *one[1] = {ctx};
+    RadauCall call(settings ? settings : &dflt, 0, nullptr);
+    call.band_call = 1;
     return multi_host_impl(one, 1, prob, B, y0, params, t0, t0_len, t1, t1_len, opt, out, &call);
 }
 

@@ -162,11 +162,16 @@ int validate(ivp_ctx *ctx, const ivp_problem_t *prob, size_t B, const ivp_option
 // what the Radau entry points hand down: the public settings, and for the DAE calls the resolved partition.  submit_impl
 // lays everything the kernels read into the argument block the context keeps (Pending::a), so neither this object nor the
 // caller's structs are looked at once the submit has returned.
+// bit 28 of IvpKArgs.ctl_nstiff as the Radau path fills it (radau_core.h uses bits 0..27: newton_maxiter, two flags, the DAE
+// partition): set by the banded call only.  No kernel reads it; ivp_jit_launch picks the band-storage module by it, for
+// every round of the solve (the argument block stays with the context).
+constexpr uint64_t IVP_RAD_BAND_CALL = 1ull << 28;
 struct RadauCall : ivp_radau_settings_t {
     int dae_call = 0;                    // ivp_radau_solve_dae*(): a problem with a mass matrix is accepted
     const ivp_radau_dae_t *dae = nullptr;
     int nind2 = 0, nind3 = 0;            // set by radau_validate
     int events_call = 0;                 // ivp_radau_solve_events*(): the one call that accepts (and requires) event functions
+    int band_call = 0;                   // ivp_radau_solve_banded*(): the one call that accepts (and requires) an IVP_RHS_BANDED problem
     RadauCall(const ivp_radau_settings_t *s, int dae_call_, const ivp_radau_dae_t *dae_) : dae_call(dae_call_), dae(dae_)
     {
         if (s) *static_cast<ivp_radau_settings_t *>(this) = *s;

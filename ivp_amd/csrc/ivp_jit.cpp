@@ -22,6 +22,9 @@
 // kernel exists in two residencies -- factors in LDS for the whole launch, or in global memory -- chosen per launch by
 // the host (IvpKArgs.lds_lu) and kept as separate modules.  A problem without the flag generates the functor text it
 // always did.
+// The banded Radau call (ivp_radau_solve_banded*) gets a Radau group module of its own for such a problem: the same tables
+// and bandwidths in the functor, bdf_band.h and radau_band.h behind radau_group.h.  The call marks its argument block
+// (IVP_RAD_BAND_CALL, ivp_ctx.h); every other Radau module generates the text it always did.
 #include "ivp_jit.h"
 
 #include <hip/hiprtc.h>
@@ -66,7 +69,7 @@ struct JitRhs {
     std::mutex mu;
     // (device, method, fp_mode, full, ctl): hipModuleLoadData binds a module to the device that is current when it is
     // loaded, so a handle shared by contexts on several GPUs keeps one module per device
-    std::map<std::tuple<int, int, int, int, bool, bool, bool>, JitModule> modules;   // ... , lane-cooperative module, banded factors in LDS
+    std::map<std::tuple<int, int, int, int, bool, bool, bool, bool>, JitModule> modules;   // ... , lane-cooperative module, banded factors in LDS, banded Radau
     std::string log;
     // the code object of the compile-only check of ivp_jit_compile (key: options + source), kept for the first launch that
     // needs exactly that module: a problem with a mass matrix checks its Radau module, which is also the one it runs
@@ -152,7 +155,7 @@ void pattern_bandwidth(int n, const int32_t *col_ptr, const int32_t *row_idx, in
         }
 }
 
-std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, bool coop_only, bool band_lds = false)
+std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, bool coop_only, bool band_lds = false, bool radau_band = false)
 {
     // kernel flavour (rk_launch.h): 2 = log-only exists for the adaptive explicit methods of problems without event functions
     const int flavour = (full_in == 2 && r.ne == 0 && (method == IVP_RK23 || method == IVP_DOPRI5 || method == IVP_DOP853)) ? 2 : (full_in ? 1 : 0);
@@ -185,13 +188,26 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
         if (radau) {   // radau_group.h: 8 < n <= 64 with G >= n lanes per trajectory, 64 < n <= 512 with G = 64 and several rows per lane
             s += join(k_src_radau_core_h);
             s += join(k_src_radau_group_h);
+            // the banded call (ivp_radau_solve_banded*, IVP_RHS_BANDED problems only): the pattern's tables and bandwidths in the
+            // functor, as in the BDF modules below, and bdf_band.h / radau_band.h behind radau_group.h.  Every other Radau
+            // module generates the text it always did.
+            std::string sp;
+            if (radau_band) {
+                s += r.sparsity_source;
+                s += join(k_src_bdf_band_h);
+                s += join(k_src_radau_band_h);
+                sp = "  enum { SP_NGROUPS = " + std::to_string(r.n_groups) + " };\n"
+                     "  static __device__ __forceinline__ int sp_group_of(int c) { return ivp_sp_group_of[c]; }\n"
+                     "  static __device__ __forceinline__ int sp_hit(int e) { return ivp_sp_hit[e]; }\n"
+                     "  enum { SP_ML = " + std::to_string(r.band_ml) + ", SP_MU = " + std::to_string(r.band_mu) + " };\n";
+            }
             std::snprintf(buf, sizeof buf,
                           "namespace ivp_jit { struct RhsUser { enum { N = %d, P = %d, NE = IVP_USER_NE };\n"
                           "  static __device__ __forceinline__ double ode_comp(int i, double x, const double* y, const double* p) { return ::ode_comp(i, x, y, p); }\n"
                           "#if IVP_USER_JAC\n"
                           "  static __device__ __forceinline__ void jac_col(int col, double x, const double* y, double* column, const double* p) { ::jac_col(col, x, y, column, p); }\n"
                           "#endif\n"
-                          "%s%s"
+                          "%s%s%s"
                           "}; }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_init(const IvpKArgs a) { ivp_jit::group_init_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n"
                           "extern \"C\" __global__ __launch_bounds__(IVP_WAVE) void ivp_jit_chunk(const IvpKArgs a) { ivp_jit::group_chunk_body<ivp_jit::M_RADAU, ivp_jit::RhsUser, %s, %d>(a); }\n",
@@ -202,6 +218,7 @@ std::string build_source(const JitRhs &r, int method, int full_in, bool ctl, boo
                           // block of IVP_WAVE lanes per launch -- bdf_group.h:31-32 states the rule).  Never a multi-wave workgroup here.
                           r.ne > 0 ? "  static __device__ __forceinline__ void events(double x, const double* y, double* g, const double* p) { ::events(x, y, g, p); }\n" : "",
                           r.has_mass_col ? "  static __device__ __forceinline__ void mass_col(int col, double* column, const double* p) { ::mass_col(col, column, p); }\n" : "",
+                          sp.c_str(),
                           flavour ? "1" : "0", ivp_group_width(r.n), flavour ? "1" : "0", ivp_group_width(r.n));
             s += buf;
             return s;
@@ -311,9 +328,9 @@ int load_module(JitRhs &r, const std::vector<char> &code, JitModule *out, bool c
     return IVP_OK;
 }
 
-int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitModule *out, bool coop_only = false, bool band_lds = false)
+int compile_module(JitRhs &r, int method, int fp_mode, int full, bool ctl, JitModule *out, bool coop_only = false, bool band_lds = false, bool radau_band = false)
 {
-    const std::string src = build_source(r, method, full, ctl, coop_only, band_lds);
+    const std::string src = build_source(r, method, full, ctl, coop_only, band_lds, radau_band);
     const std::string opt_key = r.arch + (fp_mode == IVP_FP_FAST ? "|fast" : "|strict");
     const std::string cpath = cache_path(src, opt_key);
     if (!cpath.empty()) {
@@ -488,11 +505,13 @@ hipError_t ivp_jit_launch(void *handle, int what, int method, int fp_mode, int f
         if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
         // banded problems: the BDF chunk kernel with LDS-resident factors is a module of its own (init kernels are the same in both)
         const bool band_lds = r->banded && method == IVP_BDF && a.lds_lu != 0 && band_lds_fits(r->n, r->band_ml, r->band_mu, r->ne);
-        auto key = std::make_tuple(dev, method, fp_mode, full, coop ? false : ctl, coop, band_lds);
+        // the banded Radau call (ivp_radau_solve_banded*) marks its argument block: a module of its own, in band storage
+        const bool radau_band = r->banded && method == IVP_RADAU && (a.ctl_nstiff & ivp_host::IVP_RAD_BAND_CALL) != 0;
+        auto key = std::make_tuple(dev, method, fp_mode, full, coop ? false : ctl, coop, band_lds, radau_band);
         auto it = r->modules.find(key);
         if (it == r->modules.end()) {
             JitModule nm;
-            if (compile_module(*r, method, fp_mode, full, coop ? false : ctl, &nm, coop, band_lds) != IVP_OK) return hipErrorInvalidValue;   // r->log says why (ivp_jit_last_log)
+            if (compile_module(*r, method, fp_mode, full, coop ? false : ctl, &nm, coop, band_lds, radau_band) != IVP_OK) return hipErrorInvalidValue;   // r->log says why (ivp_jit_last_log)
             it = r->modules.emplace(key, nm).first;
         }
         m = it->second;

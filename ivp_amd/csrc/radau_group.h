@@ -38,6 +38,10 @@
 // the columns whose pivot-row entry is non-zero, or whose rows k and m differ, are read and written -- a handful per pivot
 // for a tridiagonal Jacobian.  Pure ODEs with the identity mass only: a functor with mass_col stays at n <= 64.
 // RadauOps<GroupRhs<R, G>> picks the form by C at compile time; the C == 1 form is the code it always was.
+//
+// Band storage (radau_band.h, included after this header by the modules of the banded call only): a functor that carries
+// SP_ML / SP_MU (HasBand, bdf_group.h) takes RadauOpsBand at every width instead -- J and the three factors by bands in
+// global memory.  A functor without the two constants compiles to exactly what it compiled to.
 #pragma once
 
 namespace IVP_NS {
@@ -762,12 +766,18 @@ struct RadauOpsWide {
     }
 };
 
-// one row per lane with the factors in LDS (G >= n), or C rows per lane with every matrix in global memory
-template <class R, int G, bool WIDE>
+// one row per lane with the factors in LDS (G >= n), or C rows per lane with every matrix in global memory -- or, for a
+// functor that carries SP_ML / SP_MU (HasBand, bdf_group.h), band storage at every width (radau_band.h, included after
+// this header by the modules of such functors only: nothing else names RadauOpsBand)
+template <class R, int G>
+struct RadauOpsBand;
+template <class R, int G, int FORM>
 struct RadauOpsGroupSel { using type = RadauOpsLds<R, G>; };
 template <class R, int G>
-struct RadauOpsGroupSel<R, G, true> { using type = RadauOpsWide<R, G>; };
+struct RadauOpsGroupSel<R, G, 1> { using type = RadauOpsWide<R, G>; };
 template <class R, int G>
-struct RadauOps<GroupRhs<R, G>> : RadauOpsGroupSel<R, G, (GroupRhs<R, G>::N > 1)>::type {};
+struct RadauOpsGroupSel<R, G, 2> { using type = RadauOpsBand<R, G>; };
+template <class R, int G>
+struct RadauOps<GroupRhs<R, G>> : RadauOpsGroupSel<R, G, HasBand<R>::v ? 2 : (GroupRhs<R, G>::N > 1 ? 1 : 0)>::type {};
 
 }  // namespace IVP_NS

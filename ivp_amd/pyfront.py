@@ -259,7 +259,13 @@ def solve_ivp(fun: Union[api.IVP, str], t_span, y0, method=None, t_eval=None, de
     try:
         if opts.method_enum == api.Method.RADAU:   # solve.rs:224-232 "Radau": the direct per-method call (ivp_amd.Radau)
             from .radau import Radau
-            s = Radau().solve(problem, t0, tf, y0v, opts, ctx)
+            # a problem compiled in band storage (jac_sparsity= with jac_storage="banded") has its own call; every other
+            # problem takes the path it took
+            layout = getattr(problem, "jac_layout", None)
+            if isinstance(layout, dict) and layout.get("banded"):
+                s = Radau().solve_banded(problem, t0, tf, y0v, opts, ctx)
+            else:
+                s = Radau().solve(problem, t0, tf, y0v, opts, ctx)
         else:
             s = api.solve_ivp(problem, t0, tf, y0v, opts, ctx)
     except api.IvpError as e:   # solve.rs:216-221

@@ -1,8 +1,7 @@
 """``ivp_amd.Radau`` -- the direct per-method call ``RADAU::builder()...build().solve(..)`` (src/methods/radau.rs:19-127).
 
 Radau IIA(5), the L-stable 3-stage order-5 implicit Runge-Kutta method, on the device (strict arithmetic): pure ODEs with
-up to 512 states -- beyond 8 a ``DeviceIVP`` in component form (``ode_comp``, optional ``jac_col``; no ``jac_sparsity``, no
-banded storage) or ``Dense64()``: up to 64 states one matrix row per lane with the factors in LDS, from 65 to 512 (compiled
+up to 512 states -- beyond 8 a ``DeviceIVP`` in component form (``ode_comp``, optional ``jac_col``) or ``Dense64()``: up to 64 states one matrix row per lane with the factors in LDS, from 65 to 512 (compiled
 problems only) several rows per lane with J and the three factors in global memory, 4 n^2 doubles per trajectory (8 MB at
 n = 512: an allocation that fails is ``HipError``) -- and ``M y' = f(t, y)`` with a
 constant, possibly singular mass matrix -- a ``DeviceIVP(..., mass=True)`` for up to 8 states, ``mass_col=True`` (the
@@ -16,6 +15,15 @@ the device).  Event functions have ONE way in, ``solve_batch_events``: every occ
 everything a plain solve returns beside it (thread form up to 8 states, mass matrix included; component form without a mass
 hook up to 64).  Not there: events through the other Radau calls (``solve``, ``solve_batch``, ``solve_batch_logged``,
 ``solve_batch_dense`` still refuse a problem with event functions), events beyond n = 64, the multi-GPU entry points.
+
+A banded Jacobian has ONE way in as well, ``solve_batch_banded`` / ``solve_banded``: a ``DeviceIVP(..., jac_sparsity=S,
+jac_storage="banded")`` (8 < n <= 512, pure ODE, no event functions) keeps J and the three factors by bands -- (WJ + 3 W) n
+doubles per trajectory with WJ = ml + mu + 1 and W = 2 ml + mu + 1, 15 n for a tridiagonal system instead of 4 n^2 --
+forms J by grouped differences and factorises inside the band.  For a finite
+right-hand side and a pattern that holds every structurally non-zero entry the results equal ``solve_batch`` on the same
+source compiled without a pattern bit for bit.  Every other call above keeps refusing such a problem, and a pattern without
+band storage is refused by all of them.  Not there: the resumable, logged and CSR dense forms, events, mass matrices and
+index sets in band storage.
 """
 from typing import Optional, Sequence
 
@@ -76,6 +84,19 @@ class Radau:
         if not wait and not api._is_torch(y0):
             raise ValueError("wait=False needs device arrays (the host-pointer entry point copies results back at the end)")
         return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, wait=wait, _radau=self._c(), _radau_dae=self._dae(f))
+
+    def solve_batch_banded(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None, ctx: api.Context = None,
+                           out: api.BatchSolution = None) -> api.BatchSolution:
+        """``solve_batch`` in band storage (``ivp_radau_solve_banded`` / ``_device``), blocking: for a ``DeviceIVP`` compiled
+        with ``jac_sparsity=`` and ``jac_storage="banded"`` and nothing else (``ConfigError`` otherwise).  Host (numpy) or device
+        (torch) arrays; everything ``solve_batch`` returns, bit for bit what it returns for the same source without a pattern.
+        The ``nind*`` fields are not read: there is no DAE partition in band storage."""
+        return api.solve_ivp_batch(f, t0, t1, y0, params, options, ctx, out=out, _radau=self._c(), _radau_band=True)
+
+    def solve_banded(self, f: api.IVP, t0: float, t1: float, y0: Sequence[float], options: api.Options = None,
+                     ctx: api.Context = None) -> api.Solution:
+        """One trajectory through ``solve_batch_banded``: the ``Solution`` of ``solve``."""
+        return api.solve_ivp(f, t0, t1, y0, options, ctx, _radau=self._c(), _radau_band=True)
 
     def solve_batch_logged(self, f: api.IVP, t0, t1, y0, params=None, options: api.Options = None, ctx: api.Context = None,
                            out: api.BatchSolution = None, reserve: int = 0, two_pass: bool = False) -> api.BatchSolution:

@@ -276,6 +276,17 @@ extern "C" {
     pub fn ivp_radau_solve_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
                                   t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
                                   settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
+    // ... in band storage, for a problem compiled with IVP_RHS_BANDED (ivp_rhs_compile_sparse) and for nothing else: J and the
+    // three factors by bands, (WJ + 3 W) n doubles per trajectory; bit for bit the results of ivp_radau_solve* on the same
+    // source compiled without a pattern
+    pub fn ivp_radau_banded_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,
+                                  message: *mut c_char, message_len: usize) -> c_int;
+    pub fn ivp_radau_solve_banded(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                  t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                  settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t) -> c_int;
+    pub fn ivp_radau_solve_banded_device(ctx: *mut ivp_ctx_t, prob: *const ivp_problem_t, b: usize, y0: *const f64, params: *const f64,
+                                         t0: *const f64, t0_len: usize, t1: *const f64, t1_len: usize, opt: *const ivp_options_t,
+                                         settings: *const ivp_radau_settings_t, out: *mut ivp_batch_result_t, hip_stream: *mut c_void) -> c_int;
     // ... for M y' = f with a constant mass matrix (IVP_RHS_HAS_MASS) and the DAE index sets
     pub fn ivp_radau_dae_check(prob: *const ivp_problem_t, b: usize, opt: *const ivp_options_t, settings: *const ivp_radau_settings_t,
                                dae: *const ivp_radau_dae_t, message: *mut c_char, message_len: usize) -> c_int;

@@ -39,3 +39,7 @@ run radau_wide "$TOOLS/radau_wide_resources.hip" -DIVP_FAST=0 -I. &
 run radau_events "$TOOLS/radau_events_resources.hip" -DIVP_FAST=0 -I. &
 run radau_events_group "$TOOLS/radau_events_resources.hip" -DIVP_FAST=0 -DIVP_RES_GROUP -I. &
 wait
+# the band form of the group Radau kernels (radau_band.h, hiprtc modules only): a tridiagonal system at n = 12, 40, 65, 130,
+# 512 and ml = mu = 8 at n = 100: tools/radau_band_resources.hip
+run radau_band "$TOOLS/radau_band_resources.hip" -DIVP_FAST=0 -I. &
+wait
